@@ -4,6 +4,7 @@
     python bench.py --config 1 [--batch 64]                            # configs[1]: vision-branch image-only forward, 256^2
     python bench.py --config 2                                         # configs[2]: image+text contrastive step, b=256/GPU
     python bench.py --config 4 [--res 448|512] [--fp8]                 # configs[4]: long-sequence image (+text) step
+    python bench.py ... --dump-outputs DIR                             # + what the last timed step computed, DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" of configs 2-4 is the full training step on one synthetic batch that is already resident in HBM: the
@@ -283,6 +284,34 @@ def auto_batch(device, tokens_per_sample, layers, recompute, candidates, fixed_g
     return candidates[-1]
 
 
+DUMP_SAMPLE = 1 << 22  # elements kept of a larger output by --dump-outputs: 16 MB as float32 per array
+DUMP_SEED = 20240511
+
+
+def dump_sample(t, idx_cache):
+    """`t` flattened to float32 on the host: whole when it has at most DUMP_SAMPLE elements, otherwise at DUMP_SAMPLE distinct fixed
+    positions, every (n // DUMP_SAMPLE)-th from a seeded offset in the first stride (the same for every tensor of that length, so
+    params[j] and grads[j] are the same parameter)."""
+    t = t.detach().reshape(-1)
+    n = t.numel()
+    if n > DUMP_SAMPLE:
+        if n not in idx_cache:
+            stride = n // DUMP_SAMPLE
+            off = int(torch.randint(0, stride, (1,), generator=torch.Generator(device="cpu").manual_seed(DUMP_SEED)))
+            idx_cache[n] = off + torch.arange(DUMP_SAMPLE, dtype=torch.int64) * stride
+        t = t[idx_cache[n].to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def step_outputs(train, result, flat):
+    """What the timed step handed its caller in the last step: the loss, the gradients it accumulated and the parameters its optimiser
+    update left (training); the L2-normalised image embeddings (config 1's forward)."""
+    cache = {}
+    if not train:
+        return {"image_embeddings": dump_sample(result, cache)}
+    return {"loss": dump_sample(result, cache), "grads": dump_sample(flat.grads, cache), "params": dump_sample(flat.params, cache)}
+
+
 def param_checksum(flat):
     """[sum, sum of absolute values] of the flat parameter buffer in fp64, 128 M elements at a time (a whole-buffer fp64 reduction made
     torch allocate a 31 GB temporary: +29 GB peak reserved in the bench line)."""
@@ -345,7 +374,12 @@ def main():
                     help="single process, training configs: zero-grad + forwards + loss + backward of a step replayed as ONE "
                          "hipGraph (graphs.TrainStepGraph; the optimiser step stays eager).  For launch-bound small batches; the "
                          "per-launch HIP-event roofline needs eager launches and is omitted")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; a fixed seeded sample of "
+                         "%d distinct elements of the flat gradient and parameter buffers), rank 0 only" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from one_peace_amd import hip
     from one_peace_amd.criterions.contrastive import ImageTextRetrievalCriterion, TriModalContrastiveCriterion
@@ -651,6 +685,11 @@ def main():
             hip.lib().op_prof_enable(0)
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # before the skip leg below, whose steps move the parameters on
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in step_outputs(train, loss, flat).items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), v)
     prof = hip.profile_kernels.collect(4) if profiled_steps else None
     algo_bytes_timed = hip.GEMM_ALGO_BYTES[0]  # (snapshot: the skip leg below launches GEMMs too -- rounds 3-4 counted its bytes in)
     skip_leg = None

@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* ---- library ------------------------------------------------------------------------------------------------ */
-int op_abi_version(void); /* 2: per-call `tune` words replaced the process-wide knob setters; 3: op_gemm_nt_grouped, op_ln_geglu_fwd, ldd / ldh of op_ln_geglu_bwd, `out` of op_attn_bwd; 4: op_gemm_tn_grouped; 5: op_probe_mfma_rate, op_rows_gather / op_rows_merge, 16-byte rule of op_gemm_tn_grouped's C; 6: the op_probe_* entry points left for libonepeace_probe.so (include/onepeace_probe.h), op_gemm_nt_grouped answers OP_ENOTSUP for the GeGLU epilogue, op_gemm_tn_grouped_plan takes the workgroup count and tune word; 7: W / ldw / rowdot of op_gemm_tn_grouped, g0 of op_resid_bwd, op_gamma_grad_finish, op_gemm_nt_batched, op_audio_conv1_ln_gelu_fwd / _bwd; 8: the layer-scale gradient without a division -- rscale of op_gemm_tn_grouped, op_transpose_scaled + the scale member of the op_transpose_batched descriptor, op_resid_bwd leaves gamma out of dbranch when g0 is asked for, op_gamma_grad_finish lost its gamma argument; rowdot is a [N / 128][M] matrix of partial sums written once each (no atomics); 9: row tables -- a residual branch that runs on the samples stochastic depth keeps reads and writes the FULL activation matrix through op_rows_map's table instead of through packed copies: x_rows of op_layernorm_fwd / op_layernorm_bwd, dout_rows of op_resid_bwd, resid_rows / resid_rows_total of op_gemm_nt and op_gemm_nt_grouped, op_rows_merge without `upd` copies the dropped samples' rows only; op_prof_reserve */
+int op_abi_version(void); /* 2: per-call `tune` words replaced the process-wide knob setters; 3: op_gemm_nt_grouped, op_ln_geglu_fwd, ldd / ldh of op_ln_geglu_bwd, `out` of op_attn_bwd; 4: op_gemm_tn_grouped; 5: op_probe_mfma_rate, op_rows_gather / op_rows_merge, 16-byte rule of op_gemm_tn_grouped's C; 6: the op_probe_* entry points left for libonepeace_probe.so (include/onepeace_probe.h), op_gemm_nt_grouped answers OP_ENOTSUP for the GeGLU epilogue, op_gemm_tn_grouped_plan takes the workgroup count and tune word; 7: W / ldw / rowdot of op_gemm_tn_grouped, g0 of op_resid_bwd, op_gamma_grad_finish, op_gemm_nt_batched, op_audio_conv1_ln_gelu_fwd / _bwd; 8: the layer-scale gradient without a division -- rscale of op_gemm_tn_grouped, op_transpose_scaled + the scale member of the op_transpose_batched descriptor, op_resid_bwd leaves gamma out of dbranch when g0 is asked for, op_gamma_grad_finish lost its gamma argument; rowdot is a [N / 128][M] matrix of partial sums written once each (no atomics); 9: row tables -- a residual branch that runs on the samples stochastic depth keeps reads and writes the FULL activation matrix through op_rows_map's table instead of through packed copies: x_rows of op_layernorm_fwd / op_layernorm_bwd, dout_rows of op_resid_bwd, resid_rows / resid_rows_total of op_gemm_nt and op_gemm_nt_grouped, op_rows_merge without `upd` copies the dropped samples' rows only; op_prof_reserve; 10: run-to-run identical gradients -- op_relpos_bias_bwd sums the table gradient in a fixed order from pair lists instead of scattering with atomics, op_relpos_bias_bwd_ids became op_relpos_bias_fold_ids, the separate dBias kernel of op_attn_bwd adds into one slab per batch chunk */
 const char* op_last_error(void);
 
 /* Live per-kernel-family timing with HIP events recorded on the launch stream (used by bench.py's `roofline`).
@@ -228,19 +228,23 @@ int op_attn_bwd(const void* q, const void* k, const void* v, int64_t ld, const v
  * out[h][i][j] = table[bucket[i][j]][h] (bf16 [heads][S][Spad], columns >= S zero); transposed != 0 -> out[h][j][i]. */
 int op_relpos_bias_build(const void* table, const int* bucket, int64_t bucket_ld, void* out, int64_t heads, int64_t S,
                          int64_t Spad, int transposed, void* stream);
-/* dtable[bucket[i][j]][h] += dbias[h][i][j]  (fp32; dtable pre-zeroed by the caller) */
-int op_relpos_bias_bwd(const float* dbias, const int* bucket, int64_t bucket_ld, float* dtable, int64_t heads, int64_t S,
-                       int64_t Spad, void* stream);
+/* (ABI 10) dtable[r][h] = sum of dbias[h][i][j] (fp32 [heads][S][Spad]) over the positions with bucket[i][j] == r, summed in a fixed
+ * order: the same bits every run.  pos: int32 i*S + j of every position, grouped by bucket (row-major within a bucket); seg: int32
+ * [nseg + 1], segment t = pos[seg[t] .. seg[t+1]), each inside one bucket; bucket_seg: int32 [num_rel + 1], bucket r = segments
+ * bucket_seg[r] .. bucket_seg[r+1].  partial_ws: fp32 [nseg][heads] workspace.  dtable fp32 [num_rel][heads] is overwritten. */
+int op_relpos_bias_bwd(const float* dbias, int64_t S, int64_t Spad, const int* pos, const int* seg, int64_t nseg, const int* bucket_seg,
+                       int64_t num_rel, float* partial_ws, float* dtable, int64_t heads, void* stream);
 /* Per-sample images for the masked-pretraining passes (adapter/image.py:188-204,229-246, adapter/text.py, adapter/audio.py:
  * gather_features selects rows and columns preserve_ids[b] of the dense bias): out[b][h][i][j] = table[bucket[ids[b][i]][ids[b][j]]][h]
  * straight from the table -- out [B][heads][K][Kpad] bf16, pad columns zero; transposed != 0: rows = keys.  ids [B][K] int32
  * position ids (padding already mapped to a valid id, adapter/image.py:241-243; it is masked through key_pad).  The backward
- * folds the per-sample gradient slabs dbias [B][heads][K][Kpad] of op_attn_bwd into dense_ws (fp32 [heads][Sfull][Sfull], zeroed
- * by the caller; Sfull = extent of the bucket table) and scatters that onto dtable [num_rel][heads] (pre-zeroed). */
+ * (ABI 10: op_relpos_bias_fold_ids) folds the per-sample gradient slabs dbias [B][heads][K][Kpad] of op_attn_bwd into dense_ws (fp32
+ * [heads][Sfull][Sfull], zeroed by the caller; Sfull = extent of the bucket table), which op_relpos_bias_bwd (S = Spad = Sfull) then
+ * sums onto the table.  The fold adds with fp32 atomics: samples that share a position add in no fixed order. */
 int op_relpos_bias_build_ids(const void* table, const int* bucket, int64_t bucket_ld, const int* ids, void* out, int64_t B,
                              int64_t heads, int64_t K, int64_t Kpad, int transposed, void* stream);
-int op_relpos_bias_bwd_ids(const float* dbias, const int* bucket, int64_t bucket_ld, const int* ids, float* dense_ws, int64_t Sfull,
-                           float* dtable, int64_t B, int64_t heads, int64_t K, int64_t Kpad, void* stream);
+int op_relpos_bias_fold_ids(const float* dbias, const int* ids, float* dense_ws, int64_t Sfull, int64_t B, int64_t heads, int64_t K,
+                            int64_t Kpad, void* stream);
 
 /* ---- HBM-bound helpers of the layer backward -----------------------------------------------------------------------
  * (the reference gets these from autograd over transformer_layer.py:54-88,149-157) */

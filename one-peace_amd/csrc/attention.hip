@@ -1038,7 +1038,7 @@ __global__ __launch_bounds__(256) void bias_pack_kernel(const bf16_t* __restrict
 //                   dQ^T = K^T dS^T with K^T fragments by transpose-read.
 //   attn_bwd_dbias: workgroup owns a (128-query, 64-key) tile of one head and loops over the samples of its batch
 //                   chunk, accumulating dS in registers (the reference gets this from autograd's sum over the
-//                   expanded batch dim, adapter/image.py:164-171); chunks are combined with fp32 atomics.
+//                   expanded batch dim, adapter/image.py:164-171); each chunk adds into its own slab.
 // =====================================================================================================================
 struct AttnBwdArgs {
   const bf16_t* q; const bf16_t* k; const bf16_t* v; int64_t ld;
@@ -2645,7 +2645,7 @@ __global__ __launch_bounds__(PERS_NW * 64, 2) void attn_bwd_dkdv_pers_kernel(Att
 // grid (q tiles of 128, key tiles of 64, heads * batch chunks).  The bias fragment of the (head, q tile, key tile) is the
 // same for every sample of the chunk (per-sample bias images: chunks of ONE sample, gradient slab b for sample b -- the path of
 // masked pretraining with more kept tokens than the merged kernel's 384) and is loaded once; each sample's K/V tile goes through LDS once for all four waves (next
-// sample's tile in flight during the MFMAs); dS is accumulated in registers over the chunk, chunks combine by fp32 atomics.
+// sample's tile in flight during the MFMAs); dS is accumulated in registers over the chunk, each chunk into its own slab.
 __global__ __launch_bounds__(256, 2) void attn_bwd_dbias_kernel(AttnBwdArgs p) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 64 * 128];
   char* ldsK = smem;
@@ -2751,12 +2751,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dbias_kernel(AttnBwdArgs p) {
     if (qi >= p.S) continue;
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
-      // shared image: every chunk adds into the one slab; per-sample images: slab b of sample b, written by this workgroup alone
-      float* dst = p.dbias + ((p.bias_bs != 0 ? (int64_t)chunk * p.heads : 0) + h) * ((int64_t)p.S * p.Spad) + (int64_t)qi * p.Spad + k0 +
-                   kb * 16 + g * 4;
+      // slab `chunk` (per-sample images: chunks of one sample, slab b of sample b) is written by this workgroup alone: plain
+      // read-modify-write, the slabs are summed afterwards in a fixed order
+      float* dst = p.dbias + ((int64_t)chunk * p.heads + h) * ((int64_t)p.S * p.Spad) + (int64_t)qi * p.Spad + k0 + kb * 16 + g * 4;
       if (k0 + kb * 16 >= p.Spad) continue;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) atomicAdd(dst + r, acc[qb][kb][r]);
+      for (int r = 0; r < 4; ++r) dst[r] += acc[qb][kb][r];
     }
   }
 }
@@ -2828,6 +2828,16 @@ inline int dbias_chunks(int64_t B, int64_t S, int64_t heads, bool merge, bool ro
   return best;
 }
 
+// samples per workgroup of the separate dK/dV and dBias kernels: enough workgroups to fill the chip, as few batch chunks (= dbias
+// slabs of the separate dBias kernel) as possible
+inline int sep_bchunk(int64_t B, int64_t S, int64_t heads) {
+  const int64_t base = (int64_t)ceil_div(S, BQ) * ceil_div(S, BKV) * heads;
+  int chunks = (int)((1024 + base - 1) / base);
+  if (chunks < 1) chunks = 1;
+  if (chunks > B) chunks = (int)B;
+  return ceil_div(B, chunks);
+}
+
 // batch chunks (= dbias slabs) of the persistent dQ + dBias kernel: one workgroup per (chunk, head, half of the query blocks), at most
 // one workgroup per CU
 inline int pers_bwd_chunks(int64_t B, int64_t S, int64_t heads) {
@@ -2882,6 +2892,7 @@ extern "C" {
 // (the persistent dQ + dBias kernel of the 193 ... 257-token streams has its own chunk rule; which of the two kernels a call takes
 // also depends on arguments this query does not see -- the larger count is returned, slabs a kernel does not write stay zero)
 int64_t op_attn_bwd_dbias_slabs(int64_t B, int64_t S, int64_t heads, int64_t tune) {
+  if ((tune & 1) || ceil_div(S, BKV) > 6) return ceil_div(B, sep_bchunk(B, S, heads));  // the separate dBias kernel: a slab per chunk
   const int64_t n = dbias_chunks(B, S, heads, !(tune & 1), (tune & 2) != 0, (int)((tune >> 4) & 63));
   if (!(tune & 1) && !(tune & 1024) && pers_bwd_shape(S)) return max(n, (int64_t)pers_bwd_chunks(B, S, heads));
   return n;
@@ -3015,13 +3026,7 @@ int op_attn_bwd(const void* q, const void* k, const void* v, int64_t ld, const v
   a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.ldg = ldg; a.dbias = dbias;
   a.B = (int)B; a.S = (int)S; a.Spad = (int)Spad; a.heads = (int)heads; a.scale = scale;
   a.lone_keys = !(tune & 2048);
-  {  // batch chunk per workgroup: enough workgroups to fill the chip, as few atomic rounds as possible
-    const int64_t base = (int64_t)ceil_div(S, BQ) * ceil_div(S, BKV) * heads;
-    int chunks = (int)((1024 + base - 1) / base);
-    if (chunks < 1) chunks = 1;
-    if (chunks > B) chunks = (int)B;
-    a.bchunk = ceil_div(B, chunks);
-  }
+  a.bchunk = sep_bchunk(B, S, heads);
   hipStream_t s = (hipStream_t)stream;
   const double fl = 4.0 * (double)B * (double)heads * (double)S * (double)S * HD;
   int slot;

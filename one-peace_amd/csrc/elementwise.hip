@@ -565,16 +565,35 @@ __global__ __launch_bounds__(256) void relpos_build_kernel(const bf16_t* __restr
   }
 }
 
-// dtable[bucket[i][j]][h] += dbias[h][i][j]  (fp32 atomics: <= heads*S*S adds onto num_rel*heads addresses once
-// per backward; summation order is not fixed, error is fp32 round-off of a few-thousand-term sum)
-__global__ __launch_bounds__(256) void relpos_bwd_kernel(const float* __restrict__ dbias, const int* __restrict__ bucket,
-                                                         int64_t bucket_ld, float* __restrict__ dtable, int heads, int S,
-                                                         int Spad) {
-  const int64_t total = (int64_t)S * S;
+// dtable[r][h] = sum over the positions (i, j) with bucket[i][j] == r of dbias[h][i][j], in a fixed order (no atomics: the same bits
+// every run).  The caller lists the positions p = i*S + j grouped by bucket (`pos`) and cuts every bucket's list into segments of at
+// most a few dozen positions (`seg`: segment t = pos[seg[t] .. seg[t+1])); pass 1 sums each segment per head, pass 2 sums each
+// bucket's segments (`bucket_seg`: bucket r = segments bucket_seg[r] .. bucket_seg[r+1]) -- the cross-modal bucket of a joint
+// stream holds 10^5 positions, so one thread per bucket would serialise it.
+__global__ __launch_bounds__(256) void relpos_seg_sum_kernel(const float* __restrict__ dbias, const int* __restrict__ pos,
+                                                             const int* __restrict__ seg, float* __restrict__ partial, int nseg,
+                                                             int heads, int S, int Spad) {
+  const int64_t total = (int64_t)nseg * heads;
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
-    const int i = (int)(idx / S), j = (int)(idx - (int64_t)i * S);
-    const int b = bucket[(int64_t)i * bucket_ld + j];
-    for (int h = 0; h < heads; ++h) atomicAdd(&dtable[(int64_t)b * heads + h], dbias[((int64_t)h * S + i) * Spad + j]);
+    const int t = (int)(idx / heads), h = (int)(idx - (int64_t)t * heads);
+    const float* d = dbias + (int64_t)h * S * Spad;
+    float s = 0.f;
+    for (int k = seg[t], e = seg[t + 1]; k < e; ++k) {
+      const int p = pos[k], i = p / S;
+      s += d[(int64_t)i * Spad + (p - i * S)];
+    }
+    partial[idx] = s;
+  }
+}
+
+__global__ __launch_bounds__(256) void relpos_seg_fold_kernel(const float* __restrict__ partial, const int* __restrict__ bucket_seg,
+                                                              float* __restrict__ dtable, int num_rel, int heads) {
+  const int64_t total = (int64_t)num_rel * heads;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+    const int r = (int)(idx / heads), h = (int)(idx - (int64_t)r * heads);
+    float s = 0.f;
+    for (int t = bucket_seg[r], e = bucket_seg[r + 1]; t < e; ++t) s += partial[(int64_t)t * heads + h];
+    dtable[idx] = s;
   }
 }
 
@@ -602,8 +621,8 @@ __global__ __launch_bounds__(256) void relpos_build_ids_kernel(const bf16_t* __r
 }
 
 // Stage 1 of the table gradient of per-sample images: dense[h][ids[b][i]][ids[b][j]] += dbias[b][h][i][j] -- the per-sample
-// slabs are folded into ONE full-sequence image (heads x Sfull x Sfull addresses: little contention), which the ordinary
-// relpos_bwd_kernel then scatters onto the table.  (Adding the slabs straight onto the table was 29 ms per call: ten million
+// slabs are folded into ONE full-sequence image (heads x Sfull x Sfull addresses: little contention), which op_relpos_bias_bwd
+// then sums onto the table.  (fp32 atomics: the samples that share a position add in no fixed order.)  (Adding the slabs straight onto the table was 29 ms per call: ten million
 // fp32 atomics on a few thousand addresses.)
 __global__ __launch_bounds__(256) void relpos_fold_ids_kernel(const float* __restrict__ dbias, const int* __restrict__ ids,
                                                               float* __restrict__ dense, int B, int heads, int K, int Kpad, int Sfull) {
@@ -982,23 +1001,25 @@ int op_relpos_bias_build_ids(const void* table, const int* bucket, int64_t bucke
 // Table gradient from the per-sample bias gradients dbias [B][heads][K][Kpad] fp32 (one slab per sample from op_attn_bwd);
 // dtable [num_rel][heads] fp32 is accumulated into (pre-zero it).  dense_ws: fp32 [heads][Sfull][Sfull] scratch, ZEROED by the
 // caller, Sfull = extent of the bucket table the ids index (the slabs are first folded into it, then scattered onto the table).
-int op_relpos_bias_bwd_ids(const float* dbias, const int* bucket, int64_t bucket_ld, const int* ids, float* dense_ws, int64_t Sfull,
-                           float* dtable, int64_t B, int64_t heads, int64_t K, int64_t Kpad, void* stream) {
-  OP_CHECK_ARG(dbias && bucket && ids && dense_ws && dtable && B > 0 && K > 0 && Sfull > 0, "relpos_bias_bwd_ids: bad args");
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(relpos_fold_ids_kernel, dim3(ew_grid(B * heads * K * K)), dim3(256), 0, s, dbias, ids, dense_ws, (int)B,
-                     (int)heads, (int)K, (int)Kpad, (int)Sfull);
-  hipLaunchKernelGGL(relpos_bwd_kernel, dim3(ew_grid(Sfull * Sfull)), dim3(256), 0, s, (const float*)dense_ws, bucket, bucket_ld,
-                     dtable, (int)heads, (int)Sfull, (int)Sfull);
+int op_relpos_bias_fold_ids(const float* dbias, const int* ids, float* dense_ws, int64_t Sfull, int64_t B, int64_t heads, int64_t K,
+                            int64_t Kpad, void* stream) {
+  OP_CHECK_ARG(dbias && ids && dense_ws && B > 0 && K > 0 && Sfull > 0, "relpos_bias_fold_ids: bad args");
+  hipLaunchKernelGGL(relpos_fold_ids_kernel, dim3(ew_grid(B * heads * K * K)), dim3(256), 0, (hipStream_t)stream, dbias, ids, dense_ws,
+                     (int)B, (int)heads, (int)K, (int)Kpad, (int)Sfull);
   OP_LAUNCH_CHECK();
   return OP_OK;
 }
 
-int op_relpos_bias_bwd(const float* dbias, const int* bucket, int64_t bucket_ld, float* dtable, int64_t heads, int64_t S,
-                       int64_t Spad, void* stream) {
-  OP_CHECK_ARG(dbias && bucket && dtable, "relpos_bias_bwd: null pointer");
-  hipLaunchKernelGGL(relpos_bwd_kernel, dim3(ew_grid(S * S)), dim3(256), 0, (hipStream_t)stream, dbias, bucket, bucket_ld,
-                     dtable, (int)heads, (int)S, (int)Spad);
+int op_relpos_bias_bwd(const float* dbias, int64_t S, int64_t Spad, const int* pos, const int* seg, int64_t nseg, const int* bucket_seg,
+                       int64_t num_rel, float* partial_ws, float* dtable, int64_t heads, void* stream) {
+  OP_CHECK_ARG(dbias && pos && seg && bucket_seg && dtable && (partial_ws || nseg == 0), "relpos_bias_bwd: null pointer");
+  OP_CHECK_ARG(S > 0 && Spad >= S && num_rel > 0 && heads > 0 && nseg >= 0 && S * S < (1ll << 31), "relpos_bias_bwd: bad sizes");
+  hipStream_t s = (hipStream_t)stream;
+  if (nseg > 0)
+    hipLaunchKernelGGL(relpos_seg_sum_kernel, dim3(ew_grid(nseg * heads)), dim3(256), 0, s, dbias, pos, seg, partial_ws, (int)nseg,
+                       (int)heads, (int)S, (int)Spad);
+  hipLaunchKernelGGL(relpos_seg_fold_kernel, dim3(ew_grid(num_rel * heads)), dim3(256), 0, s, (const float*)partial_ws, bucket_seg,
+                     dtable, (int)num_rel, (int)heads);
   OP_LAUNCH_CHECK();
   return OP_OK;
 }

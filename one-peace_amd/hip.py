@@ -67,9 +67,9 @@ SIGNATURES = {
     "op_adamw_step_groups": (c_int, [P, P, P, P, I64, P, P, P, I64, c_float, c_float, c_float, c_float, I64, c_float, P, c_float, P]),
     "op_sqnorm": (c_int, [P, I64, P, P, P]),
     "op_relpos_bias_build": (c_int, [P, P, I64, P, I64, I64, I64, c_int, P]),
-    "op_relpos_bias_bwd": (c_int, [P, P, I64, P, I64, I64, I64, P]),
+    "op_relpos_bias_bwd": (c_int, [P, I64, I64, P, P, I64, P, I64, P, P, I64, P]),
     "op_relpos_bias_build_ids": (c_int, [P, P, I64, P, P, I64, I64, I64, I64, c_int, P]),
-    "op_relpos_bias_bwd_ids": (c_int, [P, P, I64, P, P, I64, P, I64, I64, I64, I64, P]),
+    "op_relpos_bias_fold_ids": (c_int, [P, P, P, I64, I64, I64, I64, I64, P]),
     "op_attn_fwd": (c_int, [P, P, P, I64, P, I64, P, P, P, I64, P, I64, I64, I64, I64, I64, I64, c_float, I64, P]),
     "op_attn_bias_frag_elems": (I64, [I64, I64]),
     "op_attn_bias_pack": (c_int, [P, P, I64, I64, I64, P]),
@@ -779,11 +779,42 @@ def relpos_bias_build(table, bucket_i32, S, Spad, transposed=False):
     return out
 
 
+PAIR_SEG = 32  # positions per segment of op_relpos_bias_bwd's pair lists
+
+
+def relpos_pairs(bucket_i32, S, num_rel):
+    """(pos, seg, bucket_seg, nseg) of op_relpos_bias_bwd for bucket[:S, :S]: the positions i*S + j grouped by bucket (a stable sort:
+    row-major within a bucket), cut into segments of at most PAIR_SEG.  Device work only, no host synchronisation (a joint stream
+    builds its bucket matrix every forward, possibly inside a hipGraph capture): nseg is the host-side bound S*S / PAIR_SEG + num_rel
+    on the segment count, the segments past the real ones are empty.  Cached on the bucket tensor (the adapters keep theirs)."""
+    key = (S, num_rel, bucket_i32._version)
+    cached = getattr(bucket_i32, "_op_pairs", None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    dev = bucket_i32.device
+    vals, order = torch.sort(bucket_i32[:S, :S].reshape(-1).long(), stable=True)
+    pair_off = torch.searchsorted(vals, torch.arange(num_rel + 1, device=dev))   # bucket r = sorted positions pair_off[r] .. [r+1]
+    bucket_seg = torch.zeros(num_rel + 1, dtype=torch.int64, device=dev)
+    bucket_seg[1:] = ((pair_off[1:] - pair_off[:-1] + PAIR_SEG - 1) // PAIR_SEG).cumsum(0)
+    nseg = S * S // PAIR_SEG + num_rel
+    t = torch.arange(nseg, device=dev)
+    r = torch.searchsorted(bucket_seg[1:], t, right=True)                          # bucket of segment t; num_rel past the last one
+    rc = r.clamp(max=num_rel - 1)
+    seg = torch.full((nseg + 1,), S * S, dtype=torch.int64, device=dev)
+    seg[:nseg] = torch.where(r < num_rel, pair_off[rc] + (t - bucket_seg[rc]) * PAIR_SEG, S * S)
+    res = (order.to(torch.int32), seg.to(torch.int32), bucket_seg.to(torch.int32), nseg)
+    bucket_i32._op_pairs = (key, res)
+    return res
+
+
 def relpos_bias_bwd(dbias_f32, bucket_i32, num_rel, S, Spad):
+    """Table gradient [num_rel, heads] of the bias image dbias [heads, S, Spad] (fp32), summed in a fixed order."""
     heads = dbias_f32.shape[0]
-    dtable = torch.zeros(num_rel, heads, dtype=torch.float32, device=dbias_f32.device)
-    _check(lib().op_relpos_bias_bwd(ptr(dbias_f32), ptr(bucket_i32), bucket_i32.stride(0), ptr(dtable), heads, S, Spad,
-                                    stream()), "op_relpos_bias_bwd")
+    pos, seg, bucket_seg, nseg = relpos_pairs(bucket_i32, S, num_rel)
+    dtable = torch.empty(num_rel, heads, dtype=torch.float32, device=dbias_f32.device)
+    partial = torch.empty(nseg, heads, dtype=torch.float32, device=dbias_f32.device)
+    _check(lib().op_relpos_bias_bwd(ptr(dbias_f32), S, Spad, ptr(pos), ptr(seg), nseg, ptr(bucket_seg), num_rel, ptr(partial), ptr(dtable),
+                                    heads, stream()), "op_relpos_bias_bwd")
     return dtable
 
 
@@ -799,12 +830,11 @@ def relpos_bias_build_ids(table, bucket_i32, ids_i32, Kpad, transposed=False):
 
 def relpos_bias_bwd_ids(dbias_f32, bucket_i32, ids_i32, num_rel):
     B, heads, K, Kpad = dbias_f32.shape
-    dtable = torch.zeros(num_rel, heads, dtype=torch.float32, device=dbias_f32.device)
     Sfull = bucket_i32.shape[0]
     dense = torch.zeros(heads, Sfull, Sfull, dtype=torch.float32, device=dbias_f32.device)
-    _check(lib().op_relpos_bias_bwd_ids(ptr(dbias_f32), ptr(bucket_i32), bucket_i32.stride(0), ptr(ids_i32), ptr(dense), Sfull,
-                                        ptr(dtable), B, heads, K, Kpad, stream()), "op_relpos_bias_bwd_ids")
-    return dtable
+    _check(lib().op_relpos_bias_fold_ids(ptr(dbias_f32), ptr(ids_i32), ptr(dense), Sfull, B, heads, K, Kpad, stream()),
+           "op_relpos_bias_fold_ids")
+    return relpos_bias_bwd(dense, bucket_i32, num_rel, Sfull, Sfull)
 
 
 def attn_spad(S):

@@ -64,7 +64,7 @@ def test_one_tile_launch_rule_of_multi_gpu_runs_gives_the_same_bits_over_rccl():
     tune sched 7, selected by init_distributed for world > 1 over RCCL) against the single-GPU rule (persistent workgroups), both over
     RCCL at world 1 with the collectives forced on: the two rules launch bit-identical GEMM tiles (tests/test_ops_gpu.py), so the same
     training steps must give the same loss at every step and the same parameters after the last optimiser step (checksums to 1e-9
-    relative: the relative-position table gradient is scattered with fp32 atomics, the one run-to-run freedom of the step).
+    relative).
     (VERDICT r5 #11: the rule had never run under a test.)"""
     import json
     lines = {}

@@ -1420,10 +1420,7 @@ def test_recompute_cheap_level_gives_the_same_bits_with_less_kept_memory(lock, f
         ops.set_fp8_ffn(old_fp8)
     assert res[True][0] == res[False][0]
     assert len(res[True][2]) == len(res[False][2]) > 60
-    for n, g in res[False][2].items():
-        if "rel_pos_table" in n:  # (their fold scatters the bias gradient with fp32 atomics: the last bit can differ from run to run)
-            assert rel_fro(res[True][2][n].float(), g.float()) <= 1e-3, n
-            continue
+    for n, g in res[False][2].items():  # (the relative-position tables too: their gradient is summed in a fixed order)
         assert torch.equal(res[True][2][n], g), (n, float((res[True][2][n].float() - g.float()).abs().max()))
     # per token and layer LN1(x), the sub-LayerNorm output, LN2(x) (2 H bytes each) and LN_F(GeGLU) (2 F = 4 H bytes here) are not kept:
     # 10 H bytes x layers x rows (text 16 + image 17 tokens per sample, + the audio frames) -- at the 4B dimensions (F = 4 H) 14 of 46 H

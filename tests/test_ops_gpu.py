@@ -581,6 +581,38 @@ def test_relpos_bias_build_from_position_ids():
     assert_close(dt, tr.grad, fro=1e-5, mx=1e-4, what="dtable from per-sample slabs")
 
 
+@pytest.mark.parametrize("joint", [False, True])
+def test_relpos_table_gradient_over_many_segments(joint):
+    """op_relpos_bias_bwd at the sizes of the model: the 257-token image bucket (the CLS rows / columns and the zero offset hold 256
+    positions each, eight segments of the pair lists) and a joint image + text stream, whose cross-modal bucket holds 10^5 positions
+    (thousands of segments).  Against an fp64 scatter of the same gradient, and the same bits from call to call (fixed order)."""
+    hip = hipmod()
+    heads, n = 3, 16
+    num_img = (2 * n - 1) ** 2 + 3
+    bucket = O.image_bucket_position(n, num_img).to(torch.int32)
+    num_rel = num_img
+    if joint:  # relpos.joint_handle's layout: the image block, a 64-token text block with its own rows, every other position -> zero row
+        T = 64
+        tb = (torch.arange(T)[None, :] - torch.arange(T)[:, None]).clamp(-31, 31) + 31
+        S = bucket.shape[0] + T
+        jb = torch.full((S, S), num_img + 63, dtype=torch.int32)
+        jb[:257, :257] = bucket
+        jb[257:, 257:] = tb.to(torch.int32) + num_img
+        bucket, num_rel = jb, num_img + 64
+    S = bucket.shape[0]
+    Spad = hip.attn_spad(S)
+    counts = torch.bincount(bucket.reshape(-1).long(), minlength=num_rel)
+    assert int(counts.max()) > 4 * hip.PAIR_SEG
+    dbias = torch.randn(heads, S, Spad, generator=torch.Generator().manual_seed(5))
+    ref = torch.zeros(num_rel, heads, dtype=torch.float64).index_add_(
+        0, bucket.reshape(-1).long(), dbias[:, :, :S].double().reshape(heads, -1).t())
+    b32 = bucket.to(DEV)
+    dt = hip.relpos_bias_bwd(dbias.to(DEV), b32, num_rel, S, Spad)
+    assert_close(dt, ref.float(), fro=1e-5, mx=1e-4, what="dtable")
+    assert torch.equal(hip.relpos_bias_bwd(dbias.to(DEV), b32, num_rel, S, Spad), dt)
+    assert torch.equal(hip.relpos_bias_bwd(dbias.to(DEV), b32.clone(), num_rel, S, Spad), dt)  # pair lists rebuilt: the same bits
+
+
 def _attn_ref(q, k, v, heads, scale, bias, key_pad):
     """q,k,v: [B,S,H] fp32; bias [heads,S,S]; key_pad [B,S] bool.  multihead_attention.py:102-115."""
     B, S, H = q.shape
@@ -828,10 +860,7 @@ def test_attention_backward_ignores_unspecified_pad_entries(B, S, heads, merge_d
     assert_close(dqkv2, clean.float().cpu(), fro=2e-3, mx=2e-2, what="separate delta pass")
     got = dbias.sum(0)[:, :, :S]
     assert got.isfinite().all()
-    if merge_dbias:  # slabs with plain read-modify-write: deterministic
-        assert torch.equal(got, clean_dbias[:, :, :S])
-    else:            # the separate dBias kernel adds batch chunks with fp32 atomics: order-dependent last bits
-        assert_close(got, clean_dbias[:, :, :S].cpu(), fro=1e-5, mx=1e-4, what="dbias")
+    assert torch.equal(got, clean_dbias[:, :, :S])  # merged or separate dBias kernel: one slab per batch chunk, no atomics
     out_p, _ = hip.attn_fwd(d[:, :H], d[:, H:2 * H], d[:, 2 * H:], 3 * H, B, S, heads, 0.125, bias_p, pad_d, Spad,
                             bias_frag=hip.attn_bias_pack(bias_p, S))
     assert torch.equal(out_p, out)
