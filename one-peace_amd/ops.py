@@ -3,7 +3,7 @@
 Each ``torch.autograd.Function`` here is what the host-side mirrors of the reference modules call when their
 input is a bf16 tensor on an MI355X.  Forward and backward enqueue HIP kernels on the current stream; PyTorch
 only owns the memory.  An encoder layer is two functions -- ``AttnBranchFn`` (LN, fused QKV GEMM, attention, sub-LN,
-out-proj + layer-scale/drop-path residual) and ``FfnBranchFn`` (LN, GeGLU GEMM, LN(F), down GEMM + residual) -- so that
+out-proj + layer-scale/drop-path residual) and ``FfnBranchMultiFn`` (LN, GeGLU GEMM, LN(F), down GEMM + residual) -- so that
 joint text+image / text+audio streams can route each modality's rows to its own FFN.  With ``save_acts=False`` a branch
 keeps only its input and recomputes the intermediates in backward -- the reference's ``checkpoint_activations: true``
 (pretrain_vl_3B.yaml:93, one_peace_pretrain.py:78-96); with ``save_acts=True`` (``checkpoint_activations: false``) it
@@ -231,14 +231,6 @@ def _t_pad(x2d):
     return out
 
 
-def _wgrad(dyT, xT):
-    """dW[out, in] = dy^T x from the two transposed, K-padded operands."""
-    return hip.gemm_nt(dyT, [xT])
-
-
-USE_TN_WGRAD = True
-
-
 _tail_pads = {}
 
 
@@ -269,7 +261,7 @@ def wgrad(dy, x, out=None, accumulate=False):
     K, M = dy.shape
     N = x.shape[1]
     K0 = wgrad_tn_rows(K)
-    if USE_TN_WGRAD and K0 >= 64 and hip.gemm_tn_supported(K0, M, N, dy.stride(0), x.stride(0)):
+    if K0 >= 64 and hip.gemm_tn_supported(K0, M, N, dy.stride(0), x.stride(0)):
         out = hip.gemm_tn(dy[:K0], x[:K0], out, accumulate)
         if K0 != K:
             hip.gemm_tn(_tail_pad(dy, K0, 0), _tail_pad(x, K0, 1), out, True)
@@ -359,7 +351,7 @@ _wgrad_queue = _WgradQueue()
 
 
 def _wgrad_queueable(K, M, N, ldy, ldx, grad_view):
-    return (GROUPED_WGRAD and USE_TN_WGRAD and K % 64 == 0 and K >= 64 and grad_view.stride(0) % 8 == 0 and grad_view.stride(1) == 1
+    return (GROUPED_WGRAD and K % 64 == 0 and K >= 64 and grad_view.stride(0) % 8 == 0 and grad_view.stride(1) == 1
             and grad_view.data_ptr() % 16 == 0  # op_gemm_tn_grouped's rule for C: ldc % 8 == 0, 16-byte aligned (else launch now)
             and hip.gemm_tn_supported(K, M, N, ldy, ldx))
 
@@ -787,62 +779,6 @@ def _geglu_split(Fd, fln_w):
     return GEGLU_SPLIT and fln_w is not None and Fd % 256 == 0
 
 
-def _ffn_forward(x_mid, P, S, ps2, keep, want_y=True, grad=None):
-    """out = x_mid + ps2 * g2 * W2(LN_F(gelu(LN2(x_mid) W0^T) * (LN2(x_mid) W1^T)))  on x_mid [B*S, H].
-    grad: the pass belongs to a training step (default: keep).  The GeGLU form is chosen by THAT, not by `keep`: with
-    checkpoint_activations the forward (keep = False) and its recomputation in backward (keep = True) must run the same kernels, or the
-    LayerNorm(F) statistics the gradients use are not those of the forward output.  No-grad inference keeps the fused
-    GeGLU epilogue (one store instead of three; h0 / h1 rounded to bf16 only in the split form: a bf16-level train / eval difference)."""
-    if grad is None:
-        grad = keep
-    Fd = P["w0"].shape[0]
-    h0 = h1 = None
-    fp8 = FP8_FFN and x_mid.shape[1] % 128 == 0 and Fd % 128 == 0
-    split = grad and _geglu_split(Fd, P["fln_w"])
-    xq8 = gq8 = None
-    if fp8 and split:  # (round 5) the fp8 operands come out of the kernels that produce the bf16 rows: no quantisation passes
-        xln2, mean2, rstd2, xq8 = hip.layernorm_fwd(x_mid, P["ln2_w"], P["ln2_b"], want_stats=keep, q8=True)
-    else:
-        xln2, mean2, rstd2 = hip.layernorm_fwd(x_mid, P["ln2_w"], P["ln2_b"], want_stats=keep)
-    if keep and not split:
-        h0 = torch.empty(x_mid.shape[0], Fd, dtype=x_mid.dtype, device=x_mid.device)
-        h1 = torch.empty_like(h0)
-    if split:  # plain wi_0 | wi_1 up-projection; GELU, gate and the inner LayerNorm in one HBM-bound pass
-        if fp8:  # (round 5: the fp8 variant takes the same route -- its GELU no longer sits in a GEMM epilogue either)
-            w01q, w01s = _fp8_weight_pair(P["w0"], P["w1"])
-            hh = hip.gemm_nt_fp8(xq8[0], xq8[1], [w01q], [w01s])
-            gq8 = (torch.empty(hh.shape[0], Fd, dtype=torch.uint8, device=hh.device), torch.empty(hh.shape[0], dtype=torch.float32, device=hh.device))
-        else:
-            hh = hip.gemm_nt(xln2, [P["w0"], P["w1"]], n_seg=Fd, N=2 * Fd)
-        h0, h1 = hh[:, :Fd], hh[:, Fd:]
-        gln, mean_f, rstd_f = hip.ln_geglu_fwd(h0, h1, P["fln_w"], P["fln_b"], q8=gq8)
-    elif fp8:  # opt-in: e4m3 operands with per-row scales, fp32 accumulation (csrc/fp8.hip)
-        xq, xs = hip.quant_fp8_rows(xln2)
-        (w0q, w0s), (w1q, w1s) = _fp8_weight(P["w0"]), _fp8_weight(P["w1"])
-        g = hip.gemm_nt_fp8(xq, xs, [w0q, w1q], [w0s, w1s], epilogue=hip.EPI_GEGLU, h0=h0, h1=h1)
-    else:
-        g = hip.gemm_nt(xln2, [P["w0"], P["w1"]], epilogue=hip.EPI_GEGLU, h0=h0, h1=h1)
-    if split:
-        pass
-    elif P["fln_w"] is not None:
-        gln, mean_f, rstd_f = hip.layernorm_fwd(g, P["fln_w"], P["fln_b"], want_stats=keep)
-    else:
-        gln, mean_f, rstd_f = g, None, None
-    y2 = torch.empty_like(x_mid) if keep and want_y else None
-    if fp8:
-        gq, gs = gq8 if gq8 is not None else hip.quant_fp8_rows(gln)
-        w2q, w2s = _fp8_weight(P["w2"])
-        out = hip.gemm_nt_fp8(gq, gs, [w2q], [w2s], bias=P["b2"], epilogue=hip.EPI_RESID, resid=x_mid, gamma=P["g2"], rowscale=ps2,
-                              rows_per_sample=S, h0=y2)
-    else:
-        out = hip.gemm_nt(gln, [P["w2"]], [P["b2"]], epilogue=hip.EPI_RESID, resid=x_mid, gamma=P["g2"], rowscale=ps2,
-                          rows_per_sample=S, h0=y2)
-    if not keep:
-        return out, None
-    # g (the GeGLU output) is not kept: the fused LN(F)+GeGLU backward recomputes it from h0, h1
-    return out, dict(xln2=xln2, mean2=mean2, rstd2=rstd2, h0=h0, h1=h1, gln=gln, mean_f=mean_f, rstd_f=rstd_f, y2=y2)
-
-
 def _register_direct(ctx, names, params, needs):
     """Weights whose gradient GEMM accumulates straight into the flat gradient buffer (distributed.FlatParameters).
     Keeps (name, Parameter object) pairs: saved_tensors hands back fresh tensor objects without .grad / attributes."""
@@ -881,10 +817,13 @@ def _return_grads(names, params, G, direct):
     return out
 
 
-def _resid_backward(dout, y, gamma, ps, S, gname, bname, direct, G, needs, g0=None, rows=None):
+def _resid_backward(dout, y, gamma, ps, S, gname, bname, direct, G, needs, g0=None, rows=None, fold=None):
     """Gradient of  resid + ps * gamma * (y)  w.r.t. the branch output and -- where they are wanted -- gamma and the last
     Linear's bias, in one pass.  g0 (fp32 [H]): gamma's gradient is NOT taken here (no y: dgamma_from_wgrad_ok); the kernel fills g0
-    with sum_m ps * dout for op_gamma_grad_finish instead and returns ps * dout WITHOUT gamma."""
+    with sum_m ps * dout for op_gamma_grad_finish instead and returns ps * dout WITHOUT gamma.
+    fold (a dict; one call per segment of rows that share gamma but not the bias): gamma's gradient is left to the caller -- a
+    temporary is summed into fold[gname] in fp32, an in-place accumulation is not reported -- who finishes it once, after the last
+    segment."""
     names = tuple(n for n, present in ((gname, gamma is not None and g0 is None), (bname, True)) if present and needs.get(n))
     tgt, acc = _targets(direct, *names) if names else ([], False)
     t = dict(zip(names, tgt))
@@ -892,6 +831,10 @@ def _resid_backward(dout, y, gamma, ps, S, gname, bname, direct, G, needs, g0=No
     dbias = (t[bname] if acc else True) if bname in t else None
     dy, dg, db = hip.resid_bwd(dout, y if dgamma is not None else None, gamma, ps, S, dgamma=dgamma, dbias=dbias, accumulate=acc, g0=g0,
                                dout_rows=rows)  # (rows: dout is the full matrix, the pass runs on its rows rows[m])
+    if fold is not None and gname in t:
+        if not acc:
+            fold[gname] = fold[gname] + dg.float() if gname in fold else dg.float()
+        names = tuple(n for n in names if n != gname)
     _finish(direct, G, names, tuple({gname: dg, bname: db}[n] for n in names), acc)
     return dy
 
@@ -1139,134 +1082,17 @@ class AttnBranchFn(torch.autograd.Function):
         return (dx, None, None, None, None, None, None, *dimgs, *grads)
 
 
-class FfnBranchFn(torch.autograd.Function):
-    """Second half of transformer_layer.py:165-228: x + droppath(gamma_2 * modality_ffn(LN(x))) for the rows of ONE
-    modality.  x: [B, S, H] contiguous; ps: fp32 [B] or None."""
-
-    @staticmethod
-    def forward(ctx, x, ps, save_acts, *params):
-        B, S, H = x.shape
-        P = dict(zip(FFN_PARAMS, params))
-        x2 = x.reshape(B * S, H)
-        need_grad = any(ctx.needs_input_grad) and bool(int(save_acts) & 2)
-        keep = bool(int(save_acts) & 1) and need_grad
-        needs = dict(zip(FFN_PARAMS, ctx.needs_input_grad[3:]))
-        # (needs_input_grad is also set inside torch.no_grad() -- the teacher passes of a trainable model: only the flag says "recording")
-        ctx.dg_fused = need_grad and dgamma_from_wgrad_ok([B * S], P["g2"], [P["w2"]], [P["b2"]], needs["g2"], [needs["w2"]])
-        out, acts = _ffn_forward(x2, P, S, ps, keep, want_y=needs["g2"] and not ctx.dg_fused, grad=bool(int(save_acts) & 2))
-        ctx.dims, ctx.n_params = (B, S, H), len(params)
-        ctx.direct = ()
-        if need_grad:
-            _register_direct(ctx, FFN_PARAMS, params, ctx.needs_input_grad[3:])
-        if keep:
-            if not needs["w2"] and P["fln_w"] is not None:
-                acts["gln"] = None
-            if not (needs["w0"] or needs["w1"]):
-                acts["xln2"] = None
-        ctx.cheap = keep and bool(int(save_acts) & 4)
-        if ctx.cheap:  # (set_recompute_cheap; also with the fp8 forward: backward reads the bf16 rows, which the same kernels re-create)
-            acts["xln2"] = None
-            if _geglu_split(P["w0"].shape[0], P["fln_w"]):  # LN_F(gelu(h0) * h1) comes back from the kept h0 | h1
-                acts["gln"] = None
-        _save(ctx, keep, acts, x2, ps, *params)
-        return out.view(B, S, H)
-
-    @staticmethod
-    def backward(ctx, dout):
-        x_mid, ps, *rest = ctx.saved_tensors
-        params, saved_acts = rest[:ctx.n_params], rest[ctx.n_params:]
-        B, S, H = ctx.dims
-        P = dict(zip(FFN_PARAMS, params))
-        needs = {n: bool(ng) and q is not None for n, q, ng in zip(FFN_PARAMS, params, ctx.needs_input_grad[3:])}
-        need_x = bool(ctx.needs_input_grad[0])
-        if ctx.act_names is not None:
-            A = _restore(ctx, saved_acts, ("mean_f", "rstd_f", "y2", "gln", "xln2"))
-            if ctx.cheap:
-                if needs["w0"] or needs["w1"]:
-                    A["xln2"] = hip.layernorm_fwd(x_mid, P["ln2_w"], P["ln2_b"])[0]
-                if needs["w2"] and A["gln"] is None:
-                    A["gln"] = hip.ln_geglu_fwd(A["h0"], A["h1"], P["fln_w"], P["fln_b"])[0]
-        else:
-            _, A = _ffn_forward(x_mid, P, S, ps, True, want_y=not ctx.dg_fused)
-        N = B * S
-        Fd = P["w0"].shape[0]
-        dout2 = dout.reshape(N, H)
-        if not dout2.is_contiguous():
-            dout2 = dout2.contiguous()
-        G = {}
-        weight_grad, direct = _weight_grad_fn(ctx, G)
-        if ctx.dg_fused:  # dy2 = ps * dout, WITHOUT gamma_2 (see AttnBranchFn.backward)
-            g0 = torch.empty(H, dtype=torch.float32, device=dout2.device)
-            dy2 = _resid_backward(dout2, None, P["g2"], ps, S, "g2", "b2", direct, G, needs, g0=g0)
-            rowdot, (rd_w2,) = _rowdot_slots(dout2.device, [P["w2"]])
-            weight_grad("w2", dy2, A["gln"], side=(P["w2"], rd_w2, P["g2"]),
-                        after=_gamma_finish_hook(rowdot, direct["g2"], [(P["b2"], g0)] if P["b2"] is not None else [], True))
-            w2_t = _transposed(P["w2"], scale=P["g2"])
-        else:
-            dy2 = _resid_backward(dout2, A["y2"], P["g2"], ps, S, "g2", "b2", direct, G, needs)
-            if needs["w2"]:
-                weight_grad("w2", dy2, A["gln"])
-            w2_t = None
-        dx = None
-        if need_x or any(needs[n] for n in ("ln2_w", "ln2_b", "w0", "w1", "fln_w", "fln_b")):
-            fp8b = FP8_FFN and FP8_FFN_DGRAD and H % 128 == 0 and Fd % 128 == 0  # (opt-in) the two input-gradient GEMMs on e4m3 operands
-            w2t = w2_t if w2_t is not None else _transposed(P["w2"])
-            if fp8b:
-                dgln = hip.gemm_nt_fp8(*hip.quant_fp8_rows(dy2), *[[x] for x in _fp8_derived(w2t)])
-            else:
-                dgln = hip.gemm_nt(dy2, [w2t])
-            # dh0 | dh1 as the two halves of ONE [N, 2F] matrix, in the memory order of the two weights' flat gradient views:
-            # one weight-gradient launch (288 output tiles, one fold) when those views are adjacent, and always one K = 2F
-            # input-gradient GEMM instead of two K = F launches chained through a residual epilogue
-            order = _adjacent_grads(direct, ("w0", "w1")) if needs["w0"] and needs["w1"] and Fd % 8 == 0 else None
-            cols = tuple(order) if order else ("w0", "w1")
-            dh = torch.empty(N, 2 * Fd, dtype=dgln.dtype, device=dgln.device)
-            dpart = {n: dh[:, i * Fd:(i + 1) * Fd] for i, n in enumerate(cols)}
-            if P["fln_w"] is not None:  # sub-LayerNorm(F) and GeGLU backward in one pass; g is recomputed from h0, h1
-                want = needs["fln_w"] or needs["fln_b"]
-                (tw, tb), acc = _targets(direct, "fln_w", "fln_b") if want else ((None, None), False)
-                _, _, dw_, db_ = hip.ln_geglu_bwd(dgln, A["h0"], A["h1"], P["fln_w"], A["mean_f"], A["rstd_f"], dw=tw, db=tb,
-                                                  accumulate=acc, need_wgrad=want, dh0=dpart["w0"], dh1=dpart["w1"])
-                if want:
-                    _finish(direct, G, ("fln_w", "fln_b"), (dw_, db_), acc)
-            else:
-                d0, d1 = hip.geglu_bwd(dgln, A["h0"], A["h1"])
-                dpart["w0"].copy_(d0)
-                dpart["w1"].copy_(d1)
-            if order:
-                wgrad_into(dh, A["xln2"], _span(direct, order), [direct[n] for n in order])
-            else:
-                for n in ("w0", "w1"):
-                    if needs[n]:
-                        weight_grad(n, dpart[n], A["xln2"])
-            if need_x or needs["ln2_w"] or needs["ln2_b"]:
-                w01t = _transposed(tuple(P[n] for n in cols))
-                if fp8b:
-                    dxln2 = hip.gemm_nt_fp8(*hip.quant_fp8_rows(dh), *[[x] for x in _fp8_derived(w01t)])
-                else:
-                    dxln2 = hip.gemm_nt(dh, [w01t])
-                want = needs["ln2_w"] or needs["ln2_b"]
-                (tw, tb), acc = _targets(direct, "ln2_w", "ln2_b") if want else ((None, None), False)
-                dx, dw_, db_ = hip.layernorm_bwd(dxln2, x_mid, P["ln2_w"], P["ln2_b"], A["mean2"], A["rstd2"], add=dout2, dw=tw, db=tb,
-                                                 accumulate=acc, need_wgrad=want)
-                if want:
-                    _finish(direct, G, ("ln2_w", "ln2_b"), (dw_, db_), acc)
-        if dx is None and need_x:
-            dx = dout2
-        grads = _return_grads(FFN_PARAMS, params, G, direct)
-        return (dx.view(B, S, H) if dx is not None else None, None, None, *grads)
-
-
 FFN_SHARED = ("ln2_w", "ln2_b", "g2")                       # shared by every modality (final_layer_norm, gamma_2)
 FFN_OWN = ("w0", "w1", "fln_w", "fln_b", "w2", "b2")          # one set per modality (text_ffn / image_ffn / audio_ffn)
 
 
 class FfnBranchMultiFn(torch.autograd.Function):
-    """Second half of transformer_layer.py:165-228 for a lock-step pass: x + droppath(gamma_2 * <modality>_ffn(LN(x))) on the packed
-    rows of several modalities, each segment through its OWN FFN weights.  final_layer_norm (forward and backward) runs over all
-    rows in one launch; the two narrow GEMMs of the branch -- down-projection + residual (N = H, K = F) and the input gradient of
-    wi_0 | wi_1 (N = H, K = 2F) -- are ONE grouped launch over the modalities (op_gemm_nt_grouped: a text pass alone is 192 tiles
-    on 256 CUs, the image pass 3.02 rounds); the wide ones (GeGLU up-projection, its LN(F), the input gradient of the
+    """Second half of transformer_layer.py:165-228: x + droppath(gamma_2 * <modality>_ffn(LN(x))) on the packed rows of one or more
+    modalities, each segment through its OWN FFN weights (a single stream, ffn_branch, is one segment).  final_layer_norm (forward and
+    backward) runs over all rows in one launch; with several segments the two narrow GEMMs of the branch -- down-projection + residual
+    (N = H, K = F) and the input gradient of wi_0 | wi_1 (N = H, K = 2F) -- are ONE grouped launch over the modalities
+    (op_gemm_nt_grouped: a text pass alone is 192 tiles on 256 CUs, the image pass 3.02 rounds; one segment takes op_gemm_nt, whose
+    kernel choice for a lone problem can differ); the wide ones (GeGLU up-projection, its LN(F), the input gradient of the
     down-projection) and the weight gradients stay per modality.
 
     x2: [N, H]; segs: [StreamSeg] (only row0 / B / S are used); pss: per segment fp32 [B] drop-path multipliers or None;
@@ -1274,7 +1100,11 @@ class FfnBranchMultiFn(torch.autograd.Function):
 
     @staticmethod
     def _compute(x2, segs, pss, params, keep, want_y, grad=None, xmap=None):
-        """xmap (hip.KeptRows.rowmap, not with the fp8 FFN): x2 is the FULL matrix, the branch runs on its rows xmap[r]; the returned
+        """grad: the pass belongs to a training step (default: keep).  The GeGLU form is chosen by THAT, not by `keep`: with
+        checkpoint_activations the forward (keep = False) and its recomputation in backward (keep = True) must run the same kernels, or
+        the LayerNorm(F) statistics the gradients use are not those of the forward output.  No-grad inference keeps the fused
+        GeGLU epilogue (one store instead of three; h0 / h1 rounded to bf16 only in the split form: a bf16-level train / eval difference).
+        xmap (hip.KeptRows.rowmap, not with the fp8 FFN): x2 is the FULL matrix, the branch runs on its rows xmap[r]; the returned
         `out` is a full matrix in which the rows of the kept samples are written (the others are the caller's)."""
         nseg = len(segs)
         shared = dict(zip(FFN_SHARED, params[:3]))
@@ -1284,13 +1114,16 @@ class FfnBranchMultiFn(torch.autograd.Function):
         Fd = own[0]["w0"].shape[0]
         dev, dt = x2.device, x2.dtype
         has_fln = own[0]["fln_w"] is not None
-        split = (keep if grad is None else grad) and _geglu_split(Fd, own[0]["fln_w"])  # (by the kind of pass, not by `keep`: see _ffn_forward)
-        fp8 = FP8_FFN and split and H % 256 == 0 and Fd % 256 == 0  # (round 5) the opt-in fp8 forward: training (split) form only
-        if fp8:  # all rows of all streams: the fp8 operand comes out of the LayerNorm kernel itself
+        split = (keep if grad is None else grad) and _geglu_split(Fd, own[0]["fln_w"])
+        fp8 = FP8_FFN and H % 128 == 0 and Fd % 128 == 0  # opt-in: e4m3 operands with per-row scales, fp32 accumulation (csrc/fp8.hip)
+        gq = None
+        if fp8 and split:  # (round 5) all rows of all streams: the fp8 operands come out of the kernels that produce the bf16 rows
             xln2, mean2, rstd2, (xq, xs) = hip.layernorm_fwd(x2, shared["ln2_w"], shared["ln2_b"], want_stats=keep, q8=True)
             gq, gs = torch.empty(N, Fd, dtype=torch.uint8, device=dev), torch.empty(N, dtype=torch.float32, device=dev)
         else:
             xln2, mean2, rstd2 = hip.layernorm_fwd(x2, shared["ln2_w"], shared["ln2_b"], want_stats=keep, x_rows=xmap)
+            if fp8:
+                xq, xs = hip.quant_fp8_rows(xln2)
         if split:
             hh = torch.empty(N, 2 * Fd, dtype=dt, device=dev)
             g, h0, h1 = None, hh[:, :Fd], hh[:, Fd:]
@@ -1313,7 +1146,13 @@ class FfnBranchMultiFn(torch.autograd.Function):
                 hip.ln_geglu_fwd(h0[r], h1[r], P["fln_w"], P["fln_b"], out=gln[r], mean=mean_f[r], rstd=rstd_f[r],
                                  q8=(gq[r], gs[r]) if fp8 else None)
                 continue
-            hip.gemm_nt(xln2[r], [P["w0"], P["w1"]], epilogue=hip.EPI_GEGLU, h0=h0[r] if keep else None, h1=h1[r] if keep else None, out=g[r])
+            if fp8:
+                (w0q, w0s), (w1q, w1s) = _fp8_weight(P["w0"]), _fp8_weight(P["w1"])
+                hip.gemm_nt_fp8(xq[r], xs[r], [w0q, w1q], [w0s, w1s], epilogue=hip.EPI_GEGLU, h0=h0[r] if keep else None,
+                                h1=h1[r] if keep else None, out=g[r])
+            else:
+                hip.gemm_nt(xln2[r], [P["w0"], P["w1"]], epilogue=hip.EPI_GEGLU, h0=h0[r] if keep else None, h1=h1[r] if keep else None,
+                            out=g[r])
             if has_fln:
                 hip._check(L.op_layernorm_fwd(hip.ptr(g[r]), hip.ptr(P["fln_w"]), hip.ptr(P["fln_b"]), hip.ptr(gln[r]),
                                               hip.ptr(mean_f[r]) if keep else None, hip.ptr(rstd_f[r]) if keep else None, sg.rows, Fd, 1e-5, 0,
@@ -1322,6 +1161,8 @@ class FfnBranchMultiFn(torch.autograd.Function):
         out = torch.empty_like(x2)  # (with xmap: the full matrix)
         rs = [slice(sg.row0, sg.end) for sg in segs]
         if fp8:  # one fp8 launch per modality (the grouped persistent launch is bf16 only)
+            if gq is None:
+                gq, gs = hip.quant_fp8_rows(gln)
             for sg, P, r, ps in zip(segs, own, rs, pss):
                 w2q, w2s = _fp8_weight(P["w2"])
                 hip.gemm_nt_fp8(gq[r], gs[r], [w2q], [w2s], bias=P["b2"], epilogue=hip.EPI_RESID, resid=x2[r], gamma=shared["g2"], rowscale=ps,
@@ -1329,12 +1170,12 @@ class FfnBranchMultiFn(torch.autograd.Function):
             acts = dict(xln2=xln2, mean2=mean2, rstd2=rstd2, h0=h0, h1=h1, gln=gln, mean_f=mean_f, rstd_f=rstd_f, y2=y2) if keep else None
             return out, acts
         tabs = [xmap[r] for r in rs] if xmap is not None else None  # (row tables: every problem writes ITS rows of the shared full matrix)
-        grouped = hip.gemm_nt_grouped([gln[r] for r in rs], [P["w2"] for P in own], biases=[P["b2"] for P in own],
-                                      outs=[out[r] for r in rs] if tabs is None else [out] * nseg,
-                                      epilogue=hip.EPI_RESID, h0s=[y2[r] for r in rs] if y2 is not None else None,
-                                      resids=[x2[r] for r in rs] if tabs is None else [x2] * nseg, gammas=[shared["g2"]] * nseg,
-                                      rowscales=list(pss), rows_per_sample=[sg.S for sg in segs], resid_rows=tabs)
-        if grouped is None:  # shape outside the persistent kernel: one launch per modality
+        grouped = nseg > 1 and hip.gemm_nt_grouped(
+            [gln[r] for r in rs], [P["w2"] for P in own], biases=[P["b2"] for P in own],
+            outs=[out[r] for r in rs] if tabs is None else [out] * nseg, epilogue=hip.EPI_RESID,
+            h0s=[y2[r] for r in rs] if y2 is not None else None, resids=[x2[r] for r in rs] if tabs is None else [x2] * nseg,
+            gammas=[shared["g2"]] * nseg, rowscales=list(pss), rows_per_sample=[sg.S for sg in segs], resid_rows=tabs) is not None
+        if not grouped:  # one segment, or a shape outside the persistent kernel: one launch per modality
             for i, (sg, P, r, ps) in enumerate(zip(segs, own, rs, pss)):
                 hip.gemm_nt(gln[r], [P["w2"]], [P["b2"]], epilogue=hip.EPI_RESID, resid=x2[r] if tabs is None else x2, gamma=shared["g2"],
                             rowscale=ps, rows_per_sample=sg.S, h0=y2[r] if y2 is not None else None, out=out[r] if tabs is None else out,
@@ -1379,9 +1220,9 @@ class FfnBranchMultiFn(torch.autograd.Function):
             if has_fln and not any(nd["w2@%d" % i] for i in range(nseg)):
                 acts["gln"] = None
         ctx.cheap = keep and bool(int(save_acts) & 4)
-        if ctx.cheap:  # (set_recompute_cheap)
+        if ctx.cheap:  # (set_recompute_cheap; also with the fp8 forward: backward reads the bf16 rows, which the same kernels re-create)
             acts["xln2"] = None
-            if _geglu_split(Fd, params[5]):
+            if _geglu_split(Fd, params[5]):  # LN_F(gelu(h0) * h1) comes back from the kept h0 | h1
                 acts["gln"] = None
         _save(ctx, keep, acts or {}, x2, *[ps for ps in pss], *params)
         ctx.n_ps = len(pss)
@@ -1425,36 +1266,21 @@ class FfnBranchMultiFn(torch.autograd.Function):
             needs["%s@%d" % (n, i)] for i in range(nseg) for n in ("w0", "w1", "fln_w", "fln_b"))
         dh = torch.empty(N, 2 * Fd, dtype=dt, device=dev) if upstream else None
         dgln = torch.empty(N, Fd, dtype=dt, device=dev) if upstream else None
-        colsets, dg_tmp = [], None
+        colsets = []
+        fold = {} if nseg > 1 else None  # gamma_2 is shared: its gradient accumulates over the segments
         fused = ctx.dg_fused  # gamma_2's gradient from the three down-projection weight gradients (no y2: dgamma_from_wgrad_ok)
         fp8b = FP8_FFN and FP8_FFN_DGRAD and H % 128 == 0 and Fd % 128 == 0
         (rowdot, rd_views), pairs = (_rowdot_slots(dev, [P["w2@%d" % i] for i in range(nseg)]), []) if fused else ((None, None), None)
         for i, sg in enumerate(segs):
             r = slice(sg.row0, sg.end)
             k = lambda n: "%s@%d" % (n, i)  # noqa: E731
-            # residual branch: gamma_2 is shared (its gradient accumulates over the segments), the bias is the modality's own
-            want_g, want_b = needs["g2"] and not fused, needs[k("b2")]
-            acc_g, acc_b = "g2" in direct, k("b2") in direct
-            tg = direct["g2"].grad if acc_g else (True if want_g else None)
-            tb = direct[k("b2")].grad if acc_b else (True if want_b else None)
-            if want_g and want_b and acc_g != acc_b:  # one in the flat buffer, one not: two temporaries, folded below
-                tg = tb = True
-                acc_g = acc_b = False
             g0 = None
             if fused:  # (g0 also switches the kernel to the un-scaled branch gradient: dy2 = ps * dout without gamma_2)
                 g0 = torch.empty(H, dtype=torch.float32, device=dev)
                 if P[k("b2")] is not None:
                     pairs.append((P[k("b2")], g0))
-            dy2, dg_, db_ = hip.resid_bwd(dout_full if mapped else dout[r], A["y2"][r] if want_g else None, P["g2"], pss[i], sg.S,
-                                          dgamma=tg if want_g else None, dbias=tb if want_b else None,
-                                          accumulate=(acc_g and want_g) or (acc_b and want_b), g0=g0, dout_rows=xmap[r] if mapped else None)
-            if want_g and not acc_g:
-                dg_tmp = dg_.float() if dg_tmp is None else dg_tmp + dg_.float()
-            if want_b:
-                if acc_b:
-                    _direct_grad_done(direct[k("b2")])
-                else:
-                    G[k("b2")] = db_
+            dy2 = _resid_backward(dout_full if mapped else dout[r], A["y2"][r] if A["y2"] is not None else None, P["g2"], pss[i], sg.S,
+                                  "g2", k("b2"), direct, G, needs, g0=g0, rows=xmap[r] if mapped else None, fold=fold)
             if fused:  # (the hook rides on the last segment's problem: by then every (bias, g0) pair is listed)
                 weight_grad(k("w2"), dy2, A["gln"][r], side=(P[k("w2")], rd_views[i], P["g2"]),
                             after=_gamma_finish_hook(rowdot, direct["g2"], pairs, True) if i == nseg - 1 else None)
@@ -1490,11 +1316,11 @@ class FfnBranchMultiFn(torch.autograd.Function):
                 for n in pair:
                     if needs[n]:
                         weight_grad(n, dpart[n], A["xln2"][r])
-        if needs["g2"] and not fused:
-            if "g2" in direct and dg_tmp is None:
-                _direct_grad_done(direct["g2"])
+        if fold is not None and needs["g2"] and not fused:  # the fp32 sum of temporaries (_return_grads folds it into a flat view),
+            if "g2" in fold:                                   # or every segment accumulated in place
+                G["g2"] = fold["g2"].to(dt)
             else:
-                G["g2"] = dg_tmp.to(dt)
+                _direct_grad_done(direct["g2"])
         dx = None
         if upstream and (need_x or needs["ln2_w"] or needs["ln2_b"]):
             dxln2 = torch.empty(N, H, dtype=dt, device=dev)
@@ -1503,7 +1329,7 @@ class FfnBranchMultiFn(torch.autograd.Function):
             if fp8b:  # one fp8 launch per modality (the grouped persistent launch is bf16 only)
                 for r, wt in zip(rs, wts):
                     hip.gemm_nt_fp8(*hip.quant_fp8_rows(dh[r]), *[[x] for x in _fp8_derived(wt)], out=dxln2[r])
-            elif hip.gemm_nt_grouped([dh[r] for r in rs], wts, outs=[dxln2[r] for r in rs]) is None:
+            elif nseg == 1 or hip.gemm_nt_grouped([dh[r] for r in rs], wts, outs=[dxln2[r] for r in rs]) is None:
                 for r, wt in zip(rs, wts):
                     hip.gemm_nt(dh[r], [wt], out=dxln2[r])
             want = needs["ln2_w"] or needs["ln2_b"]
@@ -1593,13 +1419,12 @@ def _save_flags(save_acts):
 
 
 def ffn_branch(x, ps, params, save_acts=False):
-    return FfnBranchFn.apply(x, ps, _save_flags(save_acts), *params)
-
-
-def encoder_layer(x, bias, key_pad, ps1, ps2, heads, params, save_acts=False):
-    """Whole single-modality layer; params in LAYER_PARAMS order."""
-    n = len(ATTN_PARAMS)
-    return ffn_branch(attn_branch(x, bias, key_pad, ps1, heads, params[:n], save_acts), ps2, params[n:], save_acts)
+    """Single stream: x [B, S, H] contiguous; ps: fp32 [B] drop-path multipliers or None; params in FFN_PARAMS order."""
+    B, S, H = x.shape
+    P = dict(zip(FFN_PARAMS, params))
+    out = ffn_branch_multi(x.reshape(B * S, H), [StreamSeg("x", B, S, 0)], [ps], [P[n] for n in FFN_SHARED], [[P[n] for n in FFN_OWN]],
+                           save_acts)
+    return out.view(B, S, H)
 
 
 # --------------------------------------------------------------------------------------------------------------

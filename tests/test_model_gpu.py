@@ -1379,8 +1379,8 @@ def test_recompute_cheap_level_gives_the_same_bits_with_less_kept_memory(lock, f
     """ops.set_recompute_cheap: the memory level between "keep everything" and checkpoint_activations -- the four
     LayerNorm-type outputs only weight gradients read (LN1(x), the attention sub-LayerNorm's output, LN2(x_mid), LN_F(gelu(h0) h1))
     are re-created in backward by the same kernels on the same kept rows.  Loss and EVERY gradient must be bit-identical to the
-    keep-everything run, and less memory must be held between forward and backward.  lock: the lock-step pass (AttnBranchFn over all
-    rows + FfnBranchMultiFn) or one pass per modality (AttnBranchFn + FfnBranchFn).  fp8 (round 6): with the opt-in fp8
+    keep-everything run, and less memory must be held between forward and backward.  lock: the lock-step pass (AttnBranchFn and
+    FfnBranchMultiFn over all rows) or one pass per modality (both with one row segment).  fp8 (round 6): with the opt-in fp8
     forward FFN the level used to be ignored silently for the FFN branch (bench.py's memory estimate assumed it); backward reads the
     bf16 rows, which the plain kernels re-create bit for bit next to what the _q8 variants wrote in the forward."""
     from one_peace_amd import ops

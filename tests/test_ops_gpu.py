@@ -1602,29 +1602,45 @@ def test_fp8_gemm_geglu(M, F_, K):
 
 def test_fp8_ffn_branch_forward_close_to_bf16_and_backward_unchanged():
     """ops.set_fp8_ffn: the fused FFN branch with its two forward GEMMs on the fp8 path stays within the variant's tolerance of
-    the bf16 branch, and the backward pass (bf16 kernels on the saved bf16 activations) still produces every gradient."""
+    the bf16 branch, and the backward pass (bf16 kernels on the saved bf16 activations) still produces every gradient.  Every fp8
+    forward route is covered: F = 512 in training (split GeGLU: the _q8 LayerNorm kernels emit the operands), F = 384 in training
+    (% 128 but not % 256: fused EPI_GEGLU epilogue with h0 / h1 kept) and a no-grad forward (fused EPI_GEGLU, nothing kept)."""
     from one_peace_amd import ops
-    H, Fd, B, S = 256, 512, 3, 40
-    torch.manual_seed(0)
-    params = [dev_bf16(1 + 0.1 * rnd(H, seed=1)), dev_bf16(0.1 * rnd(H, seed=2)), dev_bf16(rnd(Fd, H, seed=3, scale=H ** -0.5)),
-              dev_bf16(rnd(Fd, H, seed=4, scale=H ** -0.5)), dev_bf16(1 + 0.1 * rnd(Fd, seed=5)), dev_bf16(0.1 * rnd(Fd, seed=6)),
-              dev_bf16(rnd(H, Fd, seed=7, scale=Fd ** -0.5)), dev_bf16(0.1 * rnd(H, seed=8)), dev_bf16(0.5 + 0.1 * rnd(H, seed=9))]
+    H, B, S = 256, 3, 40
     x = dev_bf16(rnd(B, S, H, seed=10))
-    outs, grads = [], []
-    for on in (False, True):
-        old = ops.set_fp8_ffn(on)
-        try:
-            ps = [p.clone().requires_grad_(True) for p in params]
-            xi = x.clone().requires_grad_(True)
-            y = ops.ffn_branch(xi, None, ps, save_acts=True)
-            y.float().pow(2).sum().backward()
-            outs.append(y.detach().float())
-            grads.append([xi.grad.float()] + [p.grad.float() for p in ps])
-        finally:
-            ops.set_fp8_ffn(old)
-    assert rel_fro(outs[1] - x.float(), outs[0] - x.float()) <= 1.5 * FP8_TOL   # the branch itself, without the residual
-    for g8, g16 in zip(grads[1], grads[0]):
-        assert g8.isfinite().all() and rel_fro(g8, g16) <= 0.15  # same bf16 backward kernels on slightly different activations
+    fp8_launches = [0]
+    orig_f8 = ops.hip.gemm_nt_fp8
+
+    def counted_f8(*a, **k):
+        fp8_launches[0] += 1
+        return orig_f8(*a, **k)
+    for Fd in (512, 384):
+        torch.manual_seed(0)
+        params = [dev_bf16(1 + 0.1 * rnd(H, seed=1)), dev_bf16(0.1 * rnd(H, seed=2)), dev_bf16(rnd(Fd, H, seed=3, scale=H ** -0.5)),
+                  dev_bf16(rnd(Fd, H, seed=4, scale=H ** -0.5)), dev_bf16(1 + 0.1 * rnd(Fd, seed=5)), dev_bf16(0.1 * rnd(Fd, seed=6)),
+                  dev_bf16(rnd(H, Fd, seed=7, scale=Fd ** -0.5)), dev_bf16(0.1 * rnd(H, seed=8)), dev_bf16(0.5 + 0.1 * rnd(H, seed=9))]
+        outs, grads, evals = [], [], []
+        for on in (False, True):
+            old = ops.set_fp8_ffn(on)
+            ops.hip.gemm_nt_fp8 = counted_f8
+            try:
+                ps = [p.clone().requires_grad_(True) for p in params]
+                xi = x.clone().requires_grad_(True)
+                y = ops.ffn_branch(xi, None, ps, save_acts=True)
+                y.float().pow(2).sum().backward()
+                outs.append(y.detach().float())
+                grads.append([xi.grad.float()] + [p.grad.float() for p in ps])
+                fp8_launches[0] = 0
+                with torch.no_grad():
+                    evals.append(ops.ffn_branch(x, None, params).float())
+                assert fp8_launches[0] == (2 if on else 0), (Fd, on, fp8_launches[0])  # up-projection + down-projection
+            finally:
+                ops.set_fp8_ffn(old)
+                ops.hip.gemm_nt_fp8 = orig_f8
+        for got, want in ((outs[1], outs[0]), (evals[1], evals[0])):
+            assert rel_fro(got - x.float(), want - x.float()) <= 1.5 * FP8_TOL, Fd  # the branch itself, without the residual
+        for g8, g16 in zip(grads[1], grads[0]):
+            assert g8.isfinite().all() and rel_fro(g8, g16) <= 0.15, Fd  # same bf16 backward kernels on slightly different activations
 
 
 def test_rows_gather_and_merge_of_kept_samples():
