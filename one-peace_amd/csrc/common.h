@@ -69,8 +69,27 @@ __device__ __forceinline__ float wave_max(float v) {
 
 // ---- per-row e4m3 quantisation (csrc/fp8.hip; fused outputs of the LayerNorm kernels) -------------
 // scale = amax / 448 (1 for an all-zero row), q = e4m3(clamp(x / scale)): ONE definition for the stand-alone pass and the fused outputs.
+// A row holding a NaN or an inf gets a NaN / inf scale, so that the fp8 GEMMs' outputs stay non-finite where the bf16 GEMMs' would be
+// (the codes themselves are clamped to finite values).  The row's amax is therefore taken over the BIT PATTERNS of |x|: for non-negative
+// floats the integer order is the float order, and every NaN sorts above +inf -- an integer max propagates a NaN, fmaxf drops it.
 #define OP_FP8_MAX 448.0f
-__device__ __forceinline__ float fp8_row_scale(float amax) { return amax > 0.f ? amax * (1.0f / OP_FP8_MAX) : 1.0f; }
+__device__ __forceinline__ int fp8_amax_acc(int m, float v) { return max(m, (int)(__float_as_uint(v) & 0x7fffffffu)); }
+__device__ __forceinline__ float fp8_wave_amax(int m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
+  return __int_as_float(m);
+}
+// inv = 1 / scale.  Below amax ~ 1.3e-36 that reciprocal overflows (zeros would become 0 * inf = NaN, i.e. code -448): such a row takes
+// the scale 2^-126 instead (exact reciprocal, |x| * 2^126 < 112); every other row keeps amax / 448 bit for bit.
+__device__ __forceinline__ float fp8_row_scale(float amax, float& inv) {
+  float sc = amax == 0.f ? 1.0f : amax * (1.0f / OP_FP8_MAX);
+  inv = 1.0f / sc;
+  if (inv == __builtin_inff()) {
+    sc = 0x1p-126f;
+    inv = 0x1p126f;
+  }
+  return sc;
+}
 __device__ __forceinline__ u32x2 fp8_pack8(const float (&v)[8], float inv) {
   float e[8];
 #pragma unroll

@@ -228,7 +228,8 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Fp8Args p) {
   }
 }
 
-// Per-row e4m3 quantisation: q[r][c] = fp8(x[r][c] * 448 / amax_r), scale[r] = amax_r / 448 (1 for an all-zero row).
+// Per-row e4m3 quantisation: q[r][c] = fp8(x[r][c] * 448 / amax_r), scale[r] = amax_r / 448 (1 for an all-zero row, non-finite for a
+// row holding a non-finite value: common.h).
 // One wavefront per row, 8 bf16 per lane per pass; rows of up to 8192 columns stay in registers between the two passes.
 template <int MAXV>
 __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16_t* __restrict__ x, int64_t ldx, uint8_t* __restrict__ q,
@@ -238,19 +239,18 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16_t* __res
   if (row >= rows) return;
   const bf16_t* xr = x + row * ldx;
   float v[MAXV][8];
-  float amax = 0.f;
+  int amax = 0;  // bits of max |x| (fp8_amax_acc)
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) {
     const int c = (i * 64 + lane) * 8;
     if (c < cols) {
       Vec8<bf16_t>::load(xr + c, v[i]);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[i][j]));
+      for (int j = 0; j < 8; ++j) amax = fp8_amax_acc(amax, v[i][j]);
     }
   }
-  amax = wave_max(amax);
-  const float sc = fp8_row_scale(amax);
-  const float inv = 1.0f / sc;
+  float inv;
+  const float sc = fp8_row_scale(fp8_wave_amax(amax), inv);
   if (lane == 0) scale[row] = sc;
   uint8_t* qr = q + row * ldq;
 #pragma unroll
@@ -268,16 +268,15 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_wide_kernel(const bf16_t* 
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const bf16_t* xr = x + row * ldx;
-  float amax = 0.f;
+  int amax = 0;  // bits of max |x| (fp8_amax_acc)
   for (int c = lane * 8; c < cols; c += 512) {
     float v[8];
     Vec8<bf16_t>::load(xr + c, v);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
+    for (int j = 0; j < 8; ++j) amax = fp8_amax_acc(amax, v[j]);
   }
-  amax = wave_max(amax);
-  const float sc = fp8_row_scale(amax);
-  const float inv = 1.0f / sc;
+  float inv;
+  const float sc = fp8_row_scale(fp8_wave_amax(amax), inv);
   if (lane == 0) scale[row] = sc;
   uint8_t* qr = q + row * ldq;
   for (int c = lane * 8; c < cols; c += 512) {

@@ -55,18 +55,19 @@ __device__ __forceinline__ void group_sum2(float& a, float& b, float* red) {
   b = tb;
 }
 
+// amax of a row held by NW waves, from the per-lane fp8_amax_acc bit patterns (NaN-propagating, common.h)
 template <int NW>
-__device__ __forceinline__ float group_max(float v, float* red) {
-  v = wave_max(v);
+__device__ __forceinline__ float group_amax(int m, float* red) {
+  const float v = fp8_wave_amax(m);
   if (NW == 1) return v;
   const int wid = threadIdx.x >> 6;
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[wid] = v;
   __syncthreads();
-  float t = red[0];
+  int t = __float_as_int(red[0]);
 #pragma unroll
-  for (int i = 1; i < NW; ++i) t = fmaxf(t, red[i]);
-  return t;
+  for (int i = 1; i < NW; ++i) t = max(t, __float_as_int(red[i]));
+  return __int_as_float(t);
 }
 
 // Q8 (round 5; bf16, no GELU): the row is ALSO written as fp8 e4m3 with a per-row scale -- exactly what op_quant_fp8_rows makes of the
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
     }
     const float rstd = rsqrtf(group_sum<NW>(ss, red) * inv + eps);
     T* yr = y + row * (int64_t)cols;
-    float amax = 0.f;
+    int amax = 0;  // bits of max |output| (fp8_amax_acc)
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = (tig + G * i) * 8;
@@ -159,13 +160,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
         store_sel<T, NT>(yr + c, o);
         if constexpr (Q8) {  // the output as the next reader sees it (rounded to T); v is free now
 #pragma unroll
-          for (int j = 0; j < 8; ++j) { v[i][j] = (float)(T)o[j]; amax = fmaxf(amax, fabsf(v[i][j])); }
+          for (int j = 0; j < 8; ++j) { v[i][j] = (float)(T)o[j]; amax = fp8_amax_acc(amax, v[i][j]); }
         }
       }
     }
     if constexpr (Q8) {
-      const float sc = fp8_row_scale(group_max<NW>(amax, red));
-      const float qinv = 1.0f / sc;
+      float qinv;
+      const float sc = fp8_row_scale(group_amax<NW>(amax, red), qinv);
       uint8_t* qr = q8 + row * (int64_t)cols;
 #pragma unroll
       for (int i = 0; i < CH; ++i) {
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(NW == 1 ? 256 : 64 * NW) void ln_geglu_fwd_kernel(c
     }
     const float rstd = rsqrtf(group_sum<NW>(ss, red) * inv + eps);
     bf16_t* yr = y + row * (int64_t)cols;
-    float amax = 0.f;
+    int amax = 0;  // bits of max |output| (fp8_amax_acc)
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = (tig + G * i) * 8;
@@ -276,13 +277,13 @@ __global__ __launch_bounds__(NW == 1 ? 256 : 64 * NW) void ln_geglu_fwd_kernel(c
         Vec8<bf16_t>::store_nt(yr + c, o);
         if constexpr (Q8) {
 #pragma unroll
-          for (int j = 0; j < 8; ++j) { v[i][j] = (float)(bf16_t)o[j]; amax = fmaxf(amax, fabsf(v[i][j])); }
+          for (int j = 0; j < 8; ++j) { v[i][j] = (float)(bf16_t)o[j]; amax = fp8_amax_acc(amax, v[i][j]); }
         }
       }
     }
     if constexpr (Q8) {
-      const float sc = fp8_row_scale(group_max<NW>(amax, red));
-      const float qinv = 1.0f / sc;
+      float qinv;
+      const float sc = fp8_row_scale(group_amax<NW>(amax, red), qinv);
       uint8_t* qr = q8 + row * (int64_t)cols;
 #pragma unroll
       for (int i = 0; i < CH; ++i) {

@@ -67,6 +67,7 @@ def refresh_weight_cache():
         table, tiles = hip.transpose_table(jobs, live[0][1][2].device)
         _refresh_plan = (sig, table, len(jobs), tiles)
     hip.transpose_batched(_refresh_plan[1], _refresh_plan[2], _refresh_plan[3])
+    torch.autograd.graph.increment_version([v[2] for _, v in live])
     for k, v in live:
         _wt_cache[k] = (v[0], _wt_version(tuple(r() for r in v[0]), v[3]() if v[3] is not None else None), v[2], v[3])
     for k, (_, qs, tref) in list(_fp8_derived_cache.items()):  # fp8 copies of the transposed weights (opt-in fp8 input-gradient GEMMs)
@@ -75,7 +76,7 @@ def refresh_weight_cache():
             del _fp8_derived_cache[k]
             continue
         hip.quant_fp8_rows(t, out=qs)
-        _fp8_derived_cache[k] = (_cache_epoch, qs, tref)
+        _fp8_derived_cache[k] = ((_cache_epoch, t._version), qs, tref)
 
 
 def _wt_version(ws, scale):
@@ -106,6 +107,8 @@ def _transposed(ws, scale=None):
                 del _wt_cache[k]
     src = ws[0] if len(ws) == 1 else torch.cat([w.detach() for w in ws], dim=0)
     t = hip.transpose(src.detach(), out, scale=scale.detach() if scale is not None else None)
+    if out is not None:  # rebuilt in place through a raw pointer: tell the copies derived from it (_fp8_derived) by its version
+        torch.autograd.graph.increment_version(t)
     _wt_cache[key] = (tuple(weakref.ref(w) for w in ws), ver, t, weakref.ref(scale) if scale is not None else None)
     return t
 
@@ -139,16 +142,21 @@ def _fp8_derived(t):
     """(fp8 bytes, row scales) of a DERIVED bf16 matrix that keeps its address across optimiser steps (a cached transposed weight copy,
     _transposed).  Quantised on first use; refresh_weight_cache re-quantises every entry IN PLACE right behind the transposes it rebuilds
     (eagerly, outside any captured graph: a replayed TrainStepGraph keeps reading these addresses and must find this step's weights);
-    after invalidate_weight_cache (lazy mode) the next use re-quantises."""
+    after invalidate_weight_cache (lazy mode) or an in-place rebuild of t (its _version: _transposed bumps it) the next use re-quantises
+    into the same buffers."""
     key = (t.data_ptr(), tuple(t.shape))
+    ver = (_cache_epoch, t._version)
     hit = _fp8_derived_cache.get(key)
-    if hit is not None and hit[0] == _cache_epoch and hit[2]() is t:
+    if hit is not None and hit[2]() is t:
+        if hit[0] != ver:
+            hip.quant_fp8_rows(t, out=hit[1])
+            _fp8_derived_cache[key] = (ver, hit[1], hit[2])
         return hit[1]
-    if len(_fp8_derived_cache) > 4096:
-        _fp8_derived_cache.clear()
-        hit = None
+    if hit is None and len(_fp8_derived_cache) > 4096:  # drop the entries of copies that no longer exist; live ones keep their buffers
+        for k in [k for k, v in _fp8_derived_cache.items() if v[2]() is None]:
+            del _fp8_derived_cache[k]
     qs = hip.quant_fp8_rows(t, out=hit[1] if hit is not None else None)
-    _fp8_derived_cache[key] = (_cache_epoch, qs, weakref.ref(t))
+    _fp8_derived_cache[key] = (ver, qs, weakref.ref(t))
     return qs
 
 

@@ -1643,6 +1643,202 @@ def test_fp8_ffn_branch_forward_close_to_bf16_and_backward_unchanged():
             assert g8.isfinite().all() and rel_fro(g8, g16) <= 0.15, Fd  # same bf16 backward kernels on slightly different activations
 
 
+# ---- the fp8 input-gradient GEMMs of FfnBranchMultiFn.backward (round 6, FP8_FFN_DGRAD) at config-4 dimensions H = 1536, F = 6144:
+#   dgln  = dy2 . (g2 o W2)^T : A [M, H],  B = the transposed copy with the layer scale folded in [F, H]  (N = F, K = H)
+#   dxln2 = dh . [W0 | W1]^T  : A [M, 2F], B = the transposed concatenation [H, 2F]                       (N = H, K = 2F = 12 288)
+# M: the rows of one modality (3 x 785 / 2 x 1025 image tokens, 3 x 64 text tokens, one < 256) and the smallest multiple of 785 rows
+# that takes the four-wave 256 x 256 kernel (>= 256 tiles), written into a row slice of a larger output like out=dgln[r].
+def _f8_big(M, N, K):
+    return N % 256 == 0 and K % 256 == 0 and ((M + 255) // 256) * (N // 256) >= 256
+
+
+@pytest.mark.parametrize("M", [3 * 785, 2 * 1025, 3 * 64, 100, "fill"])
+@pytest.mark.parametrize("form,gamma", [("w2", 1e-6), ("w2", 1e-1), ("w01", None)])
+def test_fp8_gemm_at_the_input_gradient_shapes(M, form, gamma):
+    hip = hipmod()
+    H, Fd = 1536, 6144
+    if form == "w2":
+        M = 4 * 785 if M == "fill" else M
+        bt = hip.transpose(dev_bf16(rnd(H, Fd, seed=2, scale=Fd ** -0.5)), scale=dev_bf16(gamma * (1 + 0.5 * rnd(H, seed=3).abs())))
+        a = rnd(M, H, seed=1, scale=1e-3)
+    else:
+        M = 14 * 785 if M == "fill" else M
+        bt = hip.transpose(dev_bf16(torch.cat([rnd(Fd, H, seed=2, scale=H ** -0.5), rnd(Fd, H, seed=3, scale=H ** -0.5)])))
+        a = rnd(M, 2 * Fd, seed=1, scale=1e-3)
+    N, K = bt.shape
+    aq, sa = hip.quant_fp8_rows(dev_bf16(a))
+    bq, sb = hip.quant_fp8_rows(bt)
+    exact = _deq(aq.cpu(), sa.cpu()) @ _deq(bq.cpu(), sb.cpu()).t()
+    full = a @ bt.cpu().float().t()
+    kernels = (0, 1) if _f8_big(M, N, K) else (1,)
+    if form == "w01" and M > 8000:
+        assert kernels == (0, 1)
+    for small in kernels:
+        buf = torch.full((M + 80, N), 3.0, dtype=torch.bfloat16, device=DEV)
+        hip.TUNE.fp8_small = small
+        try:
+            hip.gemm_nt_fp8(aq, sa, [bq], [sb], out=buf[48:48 + M])
+            torch.cuda.synchronize()
+        finally:
+            hip.TUNE.fp8_small = 0
+        out = buf[48:48 + M]
+        assert bool((buf[:48] == 3.0).all()) and bool((buf[48 + M:] == 3.0).all()), "rows outside the output slice were written"
+        assert_close(out, exact, what="fp8 input-gradient GEMM (small=%d) vs dequantised operands" % small)
+        assert rel_fro(out.float(), full) <= FP8_TOL, (small, rel_fro(out.float(), full))
+
+
+# ---- non-finite values: the fp8 route lets them through where the bf16 route does.  A row holding a NaN / inf gets a non-finite
+# scale (codes clamped, finite); every other row is quantised bit for bit as before, so a GEMM output is non-finite exactly on the
+# rows / columns the bf16 GEMM's would be, and identical elsewhere.
+def _nan_equal(a, b):
+    return torch.equal(a.isnan(), b.isnan()) and torch.equal(a.nan_to_num(0.0), b.nan_to_num(0.0))
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf"), float("-inf")])
+@pytest.mark.parametrize("cols", [1536, 6144, 12288])  # the narrow, middle and wide quantisation kernels
+def test_fp8_quantisation_gives_a_non_finite_row_a_non_finite_scale(cols, bad):
+    hip = hipmod()
+    x = rnd(37, cols, seed=1, scale=3.0)
+    q0, s0 = hip.quant_fp8_rows(dev_bf16(x))
+    xb = x.clone()
+    xb[5, cols - 3] = bad  # last pass of the row
+    xb[20, 0] = bad        # first element
+    xb[33, cols // 2 + 5] = bad
+    xb[33, 9] = 1e30       # next to a huge finite value
+    q1, s1 = hip.quant_fp8_rows(dev_bf16(xb))
+    bad_rows = [5, 20, 33]
+    keep = [r for r in range(37) if r not in bad_rows]
+    assert not bool(s1[bad_rows].isfinite().any()), s1[bad_rows]
+    assert torch.equal(q1[keep], q0[keep]) and torch.equal(s1[keep], s0[keep])
+    assert bool((s1[bad_rows].isnan() if bad != bad else s1[bad_rows].isinf()).all()), s1[bad_rows]
+
+
+@pytest.mark.parametrize("cols", [1536, 6144, 12288])
+def test_fp8_quantisation_of_rows_below_1e_36(cols):
+    """amax / 448 of such a row has no finite reciprocal: its zeros must stay zero, its signs and magnitudes survive, codes finite."""
+    hip = hipmod()
+    x = rnd(8, cols, seed=1, scale=2.0)
+    x[2] = bf16_round(rnd(cols, seed=2) * 1e-37)
+    x[2, ::3] = 0.0
+    x[3] = bf16_round(rnd(cols, seed=3) * 3e-38)
+    x[3, 1::4] = 0.0
+    x[4] = 0.0
+    x[4, cols - 1] = -1e-39  # one bf16 subnormal
+    clean = x.clone()
+    clean[2:5] = 1.0
+    q, s = hip.quant_fp8_rows(dev_bf16(x))
+    q0, s0 = hip.quant_fp8_rows(dev_bf16(clean))
+    keep = [0, 1, 5, 6, 7]
+    assert torch.equal(q[keep], q0[keep]) and torch.equal(s[keep], s0[keep])
+    q, s = q.cpu(), s.cpu()
+    codes = q.view(torch.float8_e4m3fn).float()
+    assert bool(codes.isfinite().all()) and bool(s.isfinite().all()) and bool((s > 0).all())
+    for r in (2, 3, 4):
+        assert bool((codes[r][x[r] == 0] == 0).all()), "a zero of row %d lost its value" % r
+        assert bool((codes[r] * x[r] >= 0).all()), "a sign of row %d flipped" % r
+        assert rel_fro(_deq(q[r:r + 1], s[r:r + 1]), x[r:r + 1]) < 4e-2, r
+
+
+@pytest.mark.parametrize("rows,cols", [(300, 1536), (200, 6144)])
+def test_layernorm_q8_outputs_keep_a_non_finite_row_non_finite(rows, cols):
+    hip = hipmod()
+    x = dev_bf16(rnd(rows, cols, seed=1, scale=2.0))
+    w, b = dev_bf16(1 + 0.1 * rnd(cols, seed=2)), dev_bf16(0.1 * rnd(cols, seed=3))
+    bad_rows = [7, 100]
+    keep = [r for r in range(rows) if r not in bad_rows]
+    _, _, _, (q0, s0) = hip.layernorm_fwd(x, w, b, q8=True)
+    xb = x.clone()
+    xb[7, 11] = float("nan")
+    xb[100, cols - 1] = float("inf")
+    y1, _, _, (q1, s1) = hip.layernorm_fwd(xb, w, b, q8=True)
+    assert not bool(s1[bad_rows].isfinite().any()) and torch.equal(q1[keep], q0[keep]) and torch.equal(s1[keep], s0[keep])
+    q_ref, s_ref = hip.quant_fp8_rows(y1)
+    assert torch.equal(q1, q_ref) and _nan_equal(s1, s_ref)
+    h = dev_bf16(rnd(rows, 2 * cols, seed=4))
+    gq0 = (torch.empty(rows, cols, dtype=torch.uint8, device=DEV), torch.empty(rows, dtype=torch.float32, device=DEV))
+    gq1 = (torch.empty_like(gq0[0]), torch.empty_like(gq0[1]))
+    hip.ln_geglu_fwd(h[:, :cols], h[:, cols:], w, b, q8=gq0)
+    hb = h.clone()
+    hb[7, 3] = float("nan")              # in h0 (through the GELU)
+    hb[100, cols + 5] = float("-inf")    # in h1
+    g1, _, _ = hip.ln_geglu_fwd(hb[:, :cols], hb[:, cols:], w, b, q8=gq1)
+    assert not bool(gq1[1][bad_rows].isfinite().any())
+    assert torch.equal(gq1[0][keep], gq0[0][keep]) and torch.equal(gq1[1][keep], gq0[1][keep])
+    q_ref, s_ref = hip.quant_fp8_rows(g1)
+    assert torch.equal(gq1[0], q_ref) and _nan_equal(gq1[1], s_ref)
+
+
+@pytest.mark.parametrize("M,N,K", [(300, 1536, 6144), (2 * 1025, 6144, 1536), (4 * 785, 6144, 1536)])
+@pytest.mark.parametrize("bad_a,bad_b", [(float("nan"), float("inf")), (float("-inf"), float("nan"))])
+def test_fp8_gemm_keeps_a_non_finite_row_or_column_non_finite(M, N, K, bad_a, bad_b):
+    hip = hipmod()
+    a, b = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=K ** -0.5)
+    m, n = M // 3, N // 2 + 1
+    ab, bb = a.clone(), b.clone()
+    ab[m, K - 1] = bad_a
+    bb[n, 5] = bad_b
+    ops0 = hip.quant_fp8_rows(dev_bf16(a)) + hip.quant_fp8_rows(dev_bf16(b))
+    ops1 = hip.quant_fp8_rows(dev_bf16(ab)) + hip.quant_fp8_rows(dev_bf16(bb))
+    expect = torch.zeros(M, N, dtype=torch.bool, device=DEV)
+    expect[m] = True
+    expect[:, n] = True
+    for small in ((0, 1) if _f8_big(M, N, K) else (1,)):
+        hip.TUNE.fp8_small = small
+        try:
+            c0 = hip.gemm_nt_fp8(ops0[0], ops0[1], [ops0[2]], [ops0[3]])
+            c1 = hip.gemm_nt_fp8(ops1[0], ops1[1], [ops1[2]], [ops1[3]])
+            torch.cuda.synchronize()
+        finally:
+            hip.TUNE.fp8_small = 0
+        assert torch.equal(~c1.isfinite(), expect), (small, int((~c1.isfinite()).sum()), int(expect.sum()))
+        assert torch.equal(c1[~expect], c0[~expect]), small
+
+
+def _ffn_params(H, Fd):
+    return [dev_bf16(1 + 0.1 * rnd(H, seed=1)), dev_bf16(0.1 * rnd(H, seed=2)), dev_bf16(rnd(Fd, H, seed=3, scale=H ** -0.5)),
+            dev_bf16(rnd(Fd, H, seed=4, scale=H ** -0.5)), dev_bf16(1 + 0.1 * rnd(Fd, seed=5)), dev_bf16(0.1 * rnd(Fd, seed=6)),
+            dev_bf16(rnd(H, Fd, seed=7, scale=Fd ** -0.5)), dev_bf16(0.1 * rnd(H, seed=8)), dev_bf16(0.5 + 0.1 * rnd(H, seed=9))]
+
+
+def test_ffn_branch_lets_a_nan_row_through_on_every_route():
+    """A NaN in one token row of x (forward) or of dout (backward): on the bf16 route the whole row of the output / of dx is NaN and
+    nothing else changes.  The fp8 routes (forward only; forward and the two input-gradient GEMMs) must give the same non-finite
+    elements, and every other output row must be bit-identical to the same route's run on clean data."""
+    from one_peace_amd import ops
+    H, Fd, B, S = 256, 512, 3, 40
+    params = _ffn_params(H, Fd)
+    x, dout = dev_bf16(rnd(B, S, H, seed=10)), dev_bf16(rnd(B, S, H, seed=11))
+    xb, db = x.clone(), dout.clone()
+    xb[1, 17, 5] = float("nan")
+    db[2, 3, 100] = float("nan")
+    row_x, row_d = 1 * S + 17, 2 * S + 3
+
+    def run(xi, d):
+        ps = [p.clone().requires_grad_(True) for p in params]
+        xi = xi.clone().requires_grad_(True)
+        y = ops.ffn_branch(xi, None, ps, save_acts=True)
+        y.backward(d)
+        torch.cuda.synchronize()
+        return y.detach().view(B * S, H), xi.grad.view(B * S, H)
+
+    res = {}
+    old, old_dgrad = ops.FP8_FFN, ops.FP8_FFN_DGRAD
+    try:
+        for route, on, dgrad in (("bf16", False, False), ("fp8", True, False), ("fp8+dgrad", True, True)):
+            ops.set_fp8_ffn(on, dgrad=dgrad)
+            res[route] = run(x, dout), run(xb, dout), run(x, db)
+    finally:
+        ops.set_fp8_ffn(old, dgrad=old_dgrad)
+    (y_ref, _), (yn_ref, _), (_, dxn_ref) = res["bf16"]
+    assert bool(yn_ref[row_x].isnan().all()) and bool(dxn_ref[row_d].isnan().all())
+    for route, ((y, dx), (yn, _), (_, dxn)) in res.items():
+        assert torch.equal(~yn.isfinite(), ~yn_ref.isfinite()), route
+        assert torch.equal(~dxn.isfinite(), ~dxn_ref.isfinite()), route
+        other_x, other_d = [r for r in range(B * S) if r != row_x], [r for r in range(B * S) if r != row_d]
+        assert torch.equal(yn[other_x], y[other_x]), route
+        assert torch.equal(dxn[other_d], dx[other_d]), route
+
+
 def test_rows_gather_and_merge_of_kept_samples():
     """op_rows_gather / op_rows_merge (stochastic depth on the samples a branch keeps): three segments with their own tokens per
     sample, kept lists incl. 'all', 'one' and 'the last', packed rows rounded up to 64 with ZERO rows behind every segment;
