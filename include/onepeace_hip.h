@@ -363,6 +363,21 @@ int op_rows_map(int* map, const int* list, int64_t nseg, const int64_t* src_row0
                 const int64_t* n_kept, const int64_t* dst_rows, const int64_t* n_samples, const int64_t* list_off, int64_t dst_total,
                 void* stream);
 
+/* ---- retrieval: similarity top-k without the score matrix (csrc/retrieval.hip) ----------------------------------------------
+ * Replaces the materialised score matrix of the Recall metric (one_peace/metrics/recall.py:31-51: image_logits @ text_logits.t(),
+ * then topk(k=10, dim=1) in each direction).  Additive: op_abi_version() stays 10, no existing entry point changed.
+ * For every query row m < M of Q bf16 [M, D] (ldq) the k largest scores Q[m] . G[n] (fp32 accumulation) over the gallery G bf16 [N, D]
+ * (ldg): vals fp32 [M, k] descending, idx int32 [M, k].  Order: key = (ordered fp32 bits << 32) | ~n, larger first -- higher score,
+ * then lower n on exact ties; NaN (any) ranks above +inf, -0 equals +0.  The scores never reach global memory.  Results are
+ * bit-identical for every split count.  1 <= k <= 64, k <= N < 2^31, D % 32 == 0 (host zero-pads), ldq / ldg >= D and % 8 == 0, Q / G
+ * 16-byte aligned; else OP_EINVAL.  splits: gallery splits of the first kernel (0 = auto, at most 512; op_sim_topk_splits gives the
+ * number used); with more than one, the partial lists go to `workspace` ([M, splits, k] 64-bit keys, op_sim_topk_workspace_bytes)
+ * and a second kernel merges them. */
+int64_t op_sim_topk_splits(int64_t M, int64_t N, int64_t splits);
+int64_t op_sim_topk_workspace_bytes(int64_t M, int64_t N, int64_t k, int64_t splits);
+int op_sim_topk(const void* Q, int64_t ldq, const void* G, int64_t ldg, int64_t M, int64_t N, int64_t D, int64_t k, float* vals, int* idx,
+                void* workspace, int64_t workspace_bytes, int64_t splits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

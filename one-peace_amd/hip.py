@@ -82,6 +82,9 @@ SIGNATURES = {
     "op_rows_gather": (c_int, [P, P, P, I64, P, P, P, P, P, P, P, I64, I64, P]),
     "op_rows_merge": (c_int, [P, P, P, P, I64, P, P, P, P, P, P, P, I64, I64, P]),
     "op_rows_map": (c_int, [P, P, I64, P, P, P, P, P, P, P, I64, P]),
+    "op_sim_topk_splits": (I64, [I64, I64, I64]),
+    "op_sim_topk_workspace_bytes": (I64, [I64, I64, I64, I64]),
+    "op_sim_topk": (c_int, [P, I64, P, I64, I64, I64, I64, I64, P, P, P, I64, I64, P]),
 }
 
 
@@ -1012,6 +1015,41 @@ def rows_merge(base, upd, kr, out=None):
     _check(lib().op_rows_merge(ptr(base), ptr(upd), ptr(out), ptr(kr.lists), kr.nseg, c[0], c[1], c[2], c[3], c[4], c[5], kr._c_inv,
                                kr.full_rows, base.shape[1], stream()), "op_rows_merge")
     return out
+
+
+SIM_TOPK_MAX_K = 64
+
+
+def sim_topk(q, g, k, splits=None):
+    """(vals fp32 [M, k] descending, idx int64 [M, k]): the k largest q[m] . g[n] per query row (op_sim_topk; the [M, N] scores are
+    never formed).  q [M, D], g [N, D] bf16 CUDA with unit column stride; D is zero-padded to a multiple of 32 when needed.  Exact
+    ties: lower n first; NaN above +inf.  splits: None / 0 = the library's choice, else the gallery split count (tests)."""
+    assert q.dtype == torch.bfloat16 and g.dtype == torch.bfloat16 and q.is_cuda and g.is_cuda, "sim_topk takes bf16 CUDA tensors"
+    assert q.dim() == 2 and g.dim() == 2 and q.shape[1] == g.shape[1], "sim_topk: q [M, D] and g [N, D]"
+    M, D = q.shape
+    N = g.shape[0]
+    if not 1 <= k <= min(N, SIM_TOPK_MAX_K):
+        raise ValueError("sim_topk: need 1 <= k <= min(N, %d), got k = %d, N = %d" % (SIM_TOPK_MAX_K, k, N))
+
+    def operand(x):
+        if D % 32 or x.stride(1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+            Dp = (D + 31) // 32 * 32
+            y = torch.zeros(x.shape[0], Dp, dtype=x.dtype, device=x.device)
+            y[:, :D] = x
+            return y
+        return x
+
+    q, g = operand(q), operand(g)
+    vals = torch.empty(M, k, dtype=torch.float32, device=q.device)
+    idx = torch.empty(M, k, dtype=torch.int32, device=q.device)
+    if M == 0:
+        return vals, idx.long()
+    s = int(splits or 0)
+    ws_bytes = lib().op_sim_topk_workspace_bytes(M, N, k, s)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device) if ws_bytes else None
+    _check(lib().op_sim_topk(ptr(q), q.stride(0), ptr(g), g.stride(0), M, N, q.shape[1], k, ptr(vals), ptr(idx), ptr(ws), ws_bytes, s,
+                             stream()), "op_sim_topk")
+    return vals, idx.long()
 
 
 def mfma_rate_probe(seconds=1.0, waves_per_cu=8, data="normal", device=None):

@@ -157,6 +157,15 @@ class OnePeaceHubInterface:
             return tf[:, 0, :]
         return self.model(encoder_type=tag, **kw)
 
+    # ---- gallery search over extracted features (no reference counterpart) -------------------------------------------
+    @torch.no_grad()
+    def retrieve(self, query_features, gallery_features, k=10):
+        """(scores fp32 [M, k], indices int64 [M, k]) of the k gallery rows with the largest dot product per query row: the
+        extract_*_features outputs are L2-normalised, so this is cosine similarity.  ops.similarity_topk: on bf16 device features the
+        [M, N] score matrix is never formed; exact ties rank the lower gallery index first."""
+        from .. import ops
+        return ops.similarity_topk(query_features, gallery_features, k)
+
     # ---- hub_interface.py:206-225 ---------------------------------------------------------------------------------
     @torch.no_grad()
     def extract_text_features(self, src_tokens):

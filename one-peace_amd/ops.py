@@ -471,6 +471,23 @@ def hip_eligible(x):
 
 
 # --------------------------------------------------------------------------------------------------------------
+# retrieval: k best gallery rows per query (metrics/recall.py:31-51 without the score matrix)
+# --------------------------------------------------------------------------------------------------------------
+def similarity_topk(query, gallery, k, splits=None):
+    """(scores fp32 [M, k] descending, indices int64 [M, k]) of the k largest query[m] . gallery[n].  Exact ties: lower n first;
+    NaN ranks above +inf.  bf16 CUDA inputs run op_sim_topk (hip.sim_topk), which never forms the [M, N] scores; anything else
+    computes fp32 scores and a stable descending sort -- the same order."""
+    if hip_eligible(query) and hip_eligible(gallery):
+        return hip.sim_topk(query, gallery, k, splits=splits)
+    if not 1 <= k <= gallery.shape[0]:
+        raise ValueError("similarity_topk: need 1 <= k <= N, got k = %d, N = %d" % (k, gallery.shape[0]))
+    scores = query.float() @ gallery.float().t()
+    scores = torch.where(scores == 0, torch.zeros_like(scores), scores)  # -0 ties with +0, as in the kernel's key
+    vals, idx = torch.sort(scores, dim=1, descending=True, stable=True)
+    return vals[:, :k].contiguous(), idx[:, :k].contiguous()
+
+
+# --------------------------------------------------------------------------------------------------------------
 # LayerNorm (+ optional fused GELU)
 # --------------------------------------------------------------------------------------------------------------
 class LayerNormFn(torch.autograd.Function):
