@@ -310,7 +310,8 @@ int op_scale_rows(const void* dout, const void* gamma, const float* rowscale, in
                   int64_t M, int64_t N, void* stream);
 
 /* ---- contrastive head ----------------------------------------------------------------------------------------------
- * F.normalize(x, dim=1) of one_peace_retrieval.py:112,116,120 / one_peace_pretrain.py:165-173. */
+ * F.normalize(x, dim=1) of one_peace_retrieval.py:112,116,120 / one_peace_pretrain.py:165-173.  inv_norm[row] =
+ * 1 / max(||x||, eps), negated where ||x|| < eps: the backward of such a row is dy / eps, as clamp_min gives. */
 int op_l2norm_fwd(const void* x, void* y, float* inv_norm, int64_t rows, int64_t cols, float eps, int out_dtype, void* stream);
 int op_l2norm_bwd(const void* dy, const void* y, const float* inv_norm, void* dx, int64_t rows, int64_t cols, int y_dtype,
                   void* stream);

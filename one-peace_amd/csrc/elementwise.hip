@@ -315,7 +315,8 @@ __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const bf16_t* __restric
     for (int j = 0; j < 8; ++j) ss += v[j] * v[j];
   }
   ss = wave_sum(ss);
-  const float inv = 1.f / fmaxf(sqrtf(ss), eps);
+  const float nrm = sqrtf(ss);
+  const float inv = 1.f / fmaxf(nrm, eps);
   for (int c = lane * 8; c < cols; c += 512) {
     float v[8];
     Vec8<bf16_t>::load(x + (int64_t)row * cols + c, v);
@@ -323,10 +324,11 @@ __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const bf16_t* __restric
     for (int j = 0; j < 8; ++j) v[j] *= inv;
     Vec8<TO>::store(y + (int64_t)row * cols + c, v);
   }
-  if (lane == 0 && inv_norm) inv_norm[row] = inv;
+  if (lane == 0 && inv_norm) inv_norm[row] = nrm < eps ? -inv : inv;  // negative: the eps clamp was taken
 }
 
-// dx = inv * (dy - y * <y, dy>)   (valid while ||x|| > eps, which always holds for projected CLS features)
+// dx = inv * (dy - y * <y, dy>) while ||x|| >= eps.  Below eps the denominator is the constant eps (clamp_min passes no
+// gradient), so dx = dy / eps: the forward marks such rows with a negative inv_norm and the projection term is dropped.
 template <typename TY>
 __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const TY* __restrict__ dy, const TY* __restrict__ y,
                                                          const float* __restrict__ inv_norm, bf16_t* __restrict__ dx,
@@ -343,7 +345,11 @@ __global__ __launch_bounds__(256) void l2norm_bwd_kernel(const TY* __restrict__ 
     for (int j = 0; j < 8; ++j) dot += a[j] * b[j];
   }
   dot = wave_sum(dot);
-  const float inv = inv_norm[row];
+  float inv = inv_norm[row];
+  if (inv < 0.f) {  // clamped row
+    inv = -inv;
+    dot = 0.f;
+  }
   for (int c = lane * 8; c < cols; c += 512) {
     float a[8], b[8];
     Vec8<TY>::load(dy + (int64_t)row * cols + c, a);
@@ -884,7 +890,8 @@ int op_scale_rows(const void* dout, const void* gamma, const float* rowscale, in
   return OP_OK;
 }
 
-// y (out_dtype 0 bf16 / 1 f32) = x / max(||x||_2, eps) per row; inv_norm[rows] saved for the backward
+// y (out_dtype 0 bf16 / 1 f32) = x / max(||x||_2, eps) per row; inv_norm[rows] saved for the backward, negated where
+// ||x||_2 < eps
 int op_l2norm_fwd(const void* x, void* y, float* inv_norm, int64_t rows, int64_t cols, float eps, int out_dtype, void* stream) {
   OP_CHECK_ARG(x && y && cols % 8 == 0, "l2norm_fwd: bad args");
   if (rows == 0) return OP_OK;

@@ -726,6 +726,7 @@ def scale_rows(dout, gamma=None, rowscale=None, rows_per_sample=0):
 
 
 def l2norm_fwd(x, out_dtype=torch.bfloat16, eps=1e-12):
+    """(y, inv): inv[row] = 1 / max(||x||, eps), negative where the eps clamp was taken (l2norm_bwd then gives dy / eps)."""
     rows, cols = x.shape
     y = torch.empty(rows, cols, dtype=out_dtype, device=x.device)
     inv = torch.empty(rows, dtype=torch.float32, device=x.device)

@@ -1537,6 +1537,7 @@ class DclFn(torch.autograd.Function):
             loss_r, _, _ = hip.infonce_rows(sim, r0, label_smoothing, gscale=1.0 / m, write_grad=True)
             total += loss_r.sum()
             dstudent[r0:r0 + block] = gemm_any(sim.to(torch.bfloat16), teacher_t, out_f32=True, alpha=alpha)
+            del sim  # else the next block's sim is allocated while this one is alive: two blocks of sims at the peak
         ctx.save_for_backward(dstudent)
         ctx.dtype = student.dtype
         return total / m

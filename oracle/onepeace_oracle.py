@@ -400,6 +400,11 @@ def smoothed_nll(lprobs, target, epsilon=0.0):
     return nll.mean()
 
 
+def _wide(x):
+    """The reference's "fp32" casts (x.float(), utils.log_softmax): at least fp32, so an fp64 oracle run stays fp64."""
+    return torch.promote_types(x.dtype, torch.float32)
+
+
 def itc_loss(a_local, b_local, a_all, b_all, scale, rank=0, label_smoothing=0.0):
     """image_text_pretrain_loss.py:164-185 / image_text_retrieval_loss.py:92-112 (ATC: audio_text_*:160-181).
 
@@ -408,15 +413,37 @@ def itc_loss(a_local, b_local, a_all, b_all, scale, rank=0, label_smoothing=0.0)
     log-softmax, targets rank*bsz + i, mean of the two directions; also the argmax hit counts.
     """
     bsz = a_local.shape[0]
-    tgt = torch.arange(bsz) + bsz * rank
+    tgt = torch.arange(bsz, device=a_local.device) + bsz * rank
     sim_a2b = scale * a_local @ b_all.detach().t()
     sim_b2a = scale * b_local @ a_all.detach().t()
-    la = F.log_softmax(sim_a2b.float(), dim=-1).to(sim_a2b.dtype)
-    lb = F.log_softmax(sim_b2a.float(), dim=-1).to(sim_b2a.dtype)
+    la = F.log_softmax(sim_a2b.to(_wide(sim_a2b)), dim=-1).to(sim_a2b.dtype)
+    lb = F.log_softmax(sim_b2a.to(_wide(sim_b2a)), dim=-1).to(sim_b2a.dtype)
     loss = (smoothed_nll(la, tgt, label_smoothing) + smoothed_nll(lb, tgt, label_smoothing)) / 2
     a_ok = (sim_a2b.argmax(dim=1) == tgt).float().sum()
     b_ok = (sim_b2a.argmax(dim=1) == tgt).float().sum()
     return loss, a_ok, b_ok
+
+
+def dcl_loss(student, teacher, mask_indices, scale, label_smoothing=0.0, padding_masks=None):
+    """Masked-token contrastive (DCL) loss, image_text_pretrain_loss.py:187-208 (audio_text_*: same formula).
+
+    student/teacher: [B, L, H] features (position 0 is the CLS token and takes no part); mask_indices: bool [B, L];
+    padding_masks: bool [B, L - 1] over the non-CLS positions, or None.  The rows are the masked student tokens, the
+    columns every non-padding teacher token of the batch (no gradient), and the target of a row is the teacher token at
+    the same position.  Normalised features go back to the input dtype before the similarity, as in the reference."""
+    H = student.shape[-1]
+    s = student[:, 1:].reshape(-1, H)
+    t = teacher.detach()[:, 1:].reshape(-1, H)
+    mask = mask_indices[:, 1:].reshape(-1)
+    if padding_masks is not None:
+        keep = ~padding_masks.reshape(-1)
+        s, t, mask = s[keep], t[keep], mask[keep]
+    tgt = torch.nonzero(mask, as_tuple=False).flatten()
+    s_n = l2_normalize(s[tgt].to(_wide(s))).to(s.dtype)
+    t_n = l2_normalize(t.to(_wide(t))).to(t.dtype)
+    sim = scale * s_n @ t_n.t()
+    lp = F.log_softmax(sim.to(_wide(sim)), dim=-1).to(sim.dtype)
+    return smoothed_nll(lp, tgt, label_smoothing)
 
 
 # ------------------------------------------------------------------------------------------------
