@@ -379,6 +379,27 @@ int64_t op_sim_topk_workspace_bytes(int64_t M, int64_t N, int64_t k, int64_t spl
 int op_sim_topk(const void* Q, int64_t ldq, const void* G, int64_t ldg, int64_t M, int64_t N, int64_t D, int64_t k, float* vals, int* idx,
                 void* workspace, int64_t workspace_bytes, int64_t splits, void* stream);
 
+/* ---- image pre-processing: PIL-exact bicubic resize + ToTensor + Normalize (csrc/image.hip) ----------------------------------
+ * Replaces the hub's host transform (one_peace/models/one_peace/hub_interface.py:94-101: Resize((S, S), BICUBIC), ToTensor, Normalize
+ * with the CLIP mean / std of data/base_dataset.py:23-24) for B decoded uint8 RGB images of different sizes; bit-identical to
+ * PIL's Image.resize for 8-bit images followed by torchvision's fp32 arithmetic ((u / 255 - mean) / std, IEEE divisions) and, for
+ * bf16, a round-to-nearest-even cast.  Additive: op_abi_version() stays 10, no existing entry point changed.
+ * src: packed HWC uint8 images; image i starts at byte desc[i].src_off, and 16 readable bytes must follow its last pixel (src_bytes).
+ * desc: int64 [B][11] per image {src_off, H, W, cx_off, kx, cy_off, ky, tmp_off, row0, rows, vfirst}, on the DEVICE; desc_host: the same
+ * table in HOST memory (validated here, sizes the launches).  coef: int32 records built on the host (one-peace_amd/imageprep.py:
+ * bicubic_coeffs, Pillow's precompute_coeffs + normalize_coeffs_8bpc): S column records of 4 + kx ints at cx_off and S row records of
+ * 4 + ky ints at cy_off, each {first source sample, taps, 0, 0, 22-bit weights (|w| < 2^23), zero-padded}; kx, ky, cx_off, cy_off
+ * multiples of 4.  row0 / rows: the source rows the row records read (row0 = first row's first sample, rows up to the last row's
+ * last sample).  workspace: the uint8 intermediate, rows x S x 3 bytes per image at tmp_off (16-aligned).  vfirst = 1 (PIL's order for
+ * an image more than 100 times taller than wide that shrinks vertically): the vertical pass runs first, row0 = 0, rows = S and the
+ * intermediate is S x W x 3 bytes.
+ * out: [B, 3, S, S] bf16 (out_dtype 0) or f32 (1), or uint8 [B, S, S, 3] (2: the resized pixels; mean / stdev unused).  mean, stdev:
+ * HOST float[3].  16 <= S <= 1024, S % 16 == 0, 1 <= H, W < 2^30, B <= 65535; src, coef, out, workspace 16-byte aligned; else
+ * OP_EINVAL before anything is launched.  Two launches: the first pass into the workspace, then the second pass and the output. */
+int op_image_resize_normalize(const void* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B,
+                              const int* coef, int64_t coef_count, int64_t S, const float* mean, const float* stdev, void* out,
+                              int out_dtype, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,7 @@ SIGNATURES = {
     "op_sim_topk_splits": (I64, [I64, I64, I64]),
     "op_sim_topk_workspace_bytes": (I64, [I64, I64, I64, I64]),
     "op_sim_topk": (c_int, [P, I64, P, I64, I64, I64, I64, I64, P, P, P, I64, I64, P]),
+    "op_image_resize_normalize": (c_int, [P, I64, P, P, I64, P, I64, I64, P, P, P, c_int, P, I64, P]),
 }
 
 
@@ -1051,6 +1052,36 @@ def sim_topk(q, g, k, splits=None):
     _check(lib().op_sim_topk(ptr(q), q.stride(0), ptr(g), g.stride(0), M, N, q.shape[1], k, ptr(vals), ptr(idx), ptr(ws), ws_bytes, s,
                              stream()), "op_sim_topk")
     return vals, idx.long()
+
+
+DT_U8 = 2  # op_image_resize_normalize only: the resized uint8 pixels, [B, S, S, 3]
+_IMAGE_OUT = {torch.bfloat16: DT_BF16, torch.float32: DT_F32, torch.uint8: DT_U8}
+
+
+def image_resize_normalize(packed, mean=None, std=None, dtype=torch.bfloat16, device=None):
+    """[B, 3, S, S] bf16 / fp32 (or uint8 [B, S, S, 3] for dtype=torch.uint8) of an imageprep.PackedImages batch on a device
+    (op_image_resize_normalize): PIL's bicubic Resize((S, S)), then (u / 255 - mean) / std in fp32 and the cast, bit for bit.  The
+    packed host buffer goes to the device in ONE copy; the uint8 intermediate is a workspace of packed.workspace_bytes."""
+    if dtype not in _IMAGE_OUT:
+        raise TypeError("image_resize_normalize: dtype must be bfloat16, float32 or uint8, got %s" % dtype)
+    if dtype != torch.uint8 and (mean is None or std is None):
+        raise ValueError("image_resize_normalize: mean and std are required for a normalised output")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    B, S = len(packed), packed.size
+    out = torch.empty((B, S, S, 3) if dtype == torch.uint8 else (B, 3, S, S), dtype=dtype, device=dev)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        buf = packed.host.to(dev, non_blocking=packed.host.is_pinned())
+        ws = torch.empty(packed.workspace_bytes, dtype=torch.uint8, device=dev)
+        base = buf.data_ptr()
+        m = (c_float * 3)(*mean) if mean is not None else None
+        sd = (c_float * 3)(*std) if std is not None else None
+        _check(lib().op_image_resize_normalize(c_void_p(base), packed.src_bytes, c_void_p(base + packed.desc_off),
+                                               packed.desc.ctypes.data_as(c_void_p), B, c_void_p(base + packed.coef_off),
+                                               packed.coef_count, S, m, sd, ptr(out), _IMAGE_OUT[dtype], ptr(ws), ws.numel(), stream()),
+               "op_image_resize_normalize")
+    return out
 
 
 def mfma_rate_probe(seconds=1.0, waves_per_cu=8, data="normal", device=None):

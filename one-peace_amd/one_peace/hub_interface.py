@@ -1,11 +1,13 @@
 """Mirror of the feature-extraction surface of one_peace/models/one_peace/hub_interface.py:
 ``from_pretrained(...) -> OnePeaceHubInterface`` with ``extract_{text,image,audio,vl}_features`` (:206-225) and the dtype
-cast of :107-122.  Raw-data pre-processing (BPE, CLIP resize, 16 kHz layer-normed waveforms, :134-193) stays with the
-reference's Python (PIL / torchvision / librosa are not part of the hot path); the ``process_*`` methods here accept
-already-tokenised / already-decoded tensors and do the collation only."""
+cast of :107-122.  ``process_image`` (:150-168) takes image files, PIL images or decoded uint8 arrays and runs the reference's
+transform (:94-101) -- on a device through the HIP resize kernel (ops.preprocess_images), bit for bit; ``process_text`` takes
+token ids (no BPE) and ``process_audio`` decoded 16 kHz waveforms (no librosa), and do the collation only."""
 import math
+import os
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -97,8 +99,48 @@ class OnePeaceHubInterface:
             out[i, : len(t)] = t
         return out.to(self.device)
 
-    def process_image(self, images):
-        return self.cast_data_dtype(torch.as_tensor(images).to(self.device))
+    @property
+    def patch_image_size(self):
+        """S of the image transform: the model's image adapter covers S / 16 patches per side (build_from_checkpoint_cfg)."""
+        return int(self.model.cfg.encoder.image_adapter.rel_bucket_size) * 16
+
+    def process_image(self, image_list, return_image_sizes=False):
+        """hub_interface.py:150-168: Resize((S, S), BICUBIC) + ToTensor + Normalize(CLIP mean / std) of each image, stacked to
+        [B, 3, S, S] on self.device in the hub dtype (S = patch_image_size); with return_image_sizes also the widths and heights of
+        the inputs.  Items: file paths (decoded on the host with PIL, .convert("RGB")), PIL images, or uint8 [H, W, 3] RGB arrays /
+        tensors (a uint8 [B, H, W, 3] batch works too; arrays never need PIL on a device).  On a device the resize and the
+        normalisation run in op_image_resize_normalize (bit-identical to PIL + torchvision); on the CPU PIL does the resize.
+        A floating-point tensor is taken as already pre-processed and only moved and cast, as before.
+        Out of scope: JPEG / PNG decoding stays in PIL on the host; process_audio from files (librosa's soxr resampler), BPE for
+        process_text and training-time augmentation (RandomResizedCrop, RandAugment) are not provided."""
+        from .. import ops
+        if torch.is_tensor(image_list) or isinstance(image_list, np.ndarray):
+            batch = torch.as_tensor(image_list)
+            if batch.is_floating_point():
+                return self.cast_data_dtype(batch.to(self.device))
+        items = [self._decoded(im) for im in image_list]
+        widths = [im.size[0] if ops._is_pil(im) else int(im.shape[1]) for im in items]
+        heights = [im.size[1] if ops._is_pil(im) else int(im.shape[0]) for im in items]
+        src_images = ops.preprocess_images(items, self.patch_image_size, dtype=self.dtype, device=self.device)
+        if return_image_sizes:
+            return src_images, torch.tensor(widths).to(self.device), torch.tensor(heights).to(self.device)
+        return src_images
+
+    @staticmethod
+    def _decoded(item):
+        if isinstance(item, (str, bytes, os.PathLike)):
+            from PIL import Image
+            with Image.open(item) as im:
+                return im.convert("RGB")
+        return item
+
+    def process_image_text_pairs(self, image_text_list, return_image_sizes=False):
+        """hub_interface.py:195-204: ((src_images[, widths, heights]), src_tokens) of (image, token ids) pairs."""
+        src_tokens = self.process_text([pair[1] for pair in image_text_list])
+        images = [pair[0] for pair in image_text_list]
+        if return_image_sizes:
+            return self.process_image(images, return_image_sizes=True), src_tokens
+        return self.process_image(images), src_tokens
 
     def _feature_encoder_spec(self):
         """The conv stack [(dim, kernel, stride), ...] of the model's audio adapter (hub_interface.py:116-118)."""

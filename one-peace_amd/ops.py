@@ -488,6 +488,40 @@ def similarity_topk(query, gallery, k, splits=None):
 
 
 # --------------------------------------------------------------------------------------------------------------
+# image pre-processing: hub_interface.py:94-101 (Resize((S, S), BICUBIC), ToTensor, Normalize) on decoded images
+# --------------------------------------------------------------------------------------------------------------
+def _is_pil(im):
+    return type(im).__module__.startswith("PIL.") and hasattr(im, "convert")
+
+
+def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, device="cpu"):
+    """[B, 3, size, size] in `dtype` on `device` from decoded RGB images (uint8 [H, W, 3] arrays / tensors or PIL images of any
+    size): PIL's Image.resize((size, size), BICUBIC), ToTensor and Normalize (CLIP mean / std by default) in torchvision's fp32
+    order, then the cast -- the reference's transform, bit for bit.  On a CUDA device this is op_image_resize_normalize
+    (hip.image_resize_normalize: one H2D copy of the uint8 pixels, resize and normalisation on the GPU; PIL is not needed for
+    arrays); on the CPU it is PIL itself and the same torch arithmetic (the reference's own path)."""
+    import numpy as np
+
+    from . import imageprep
+    mean = imageprep.CLIP_MEAN if mean is None else tuple(mean)
+    std = imageprep.CLIP_STD if std is None else tuple(std)
+    imageprep.check_size(size)
+    dev = torch.device(device)
+    if dev.type == "cuda":
+        arrs = [np.asarray(im.convert("RGB")) if _is_pil(im) else im for im in images]
+        packed = imageprep.pack_images(arrs, size)
+        kdt = dtype if dtype in (torch.bfloat16, torch.float32) else torch.float32
+        return hip.image_resize_normalize(packed, mean, std, kdt, dev).to(dtype)
+    from PIL import Image
+    out = []
+    for im in images:
+        im = im.convert("RGB") if _is_pil(im) else Image.fromarray(imageprep.as_rgb_array(im))
+        u8 = torch.from_numpy(np.array(im.resize((size, size), Image.BICUBIC), dtype=np.uint8))
+        out.append(imageprep.to_tensor_normalize(u8, mean, std))
+    return torch.stack(out).to(device=dev, dtype=dtype) if out else torch.empty(0, 3, size, size, dtype=dtype, device=dev)
+
+
+# --------------------------------------------------------------------------------------------------------------
 # LayerNorm (+ optional fused GELU)
 # --------------------------------------------------------------------------------------------------------------
 class LayerNormFn(torch.autograd.Function):
