@@ -400,6 +400,25 @@ int op_image_resize_normalize(const void* src, int64_t src_bytes, const int64_t*
                               const int* coef, int64_t coef_count, int64_t S, const float* mean, const float* stdev, void* out,
                               int out_dtype, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- audio pre-processing: channel mean + whole-clip layer norm + crop / tile / pad (csrc/audioprep.hip) -----------------------
+ * Replaces the host loop of one_peace/models/one_peace/hub_interface.py:170-193 and data/base_dataset.py:84-102 (audio_postprocess:
+ * feats.mean(-1), F.layer_norm(feats, feats.shape) over the WHOLE clip, crop to max_len samples from the start, repeat the normalised
+ * clip up to min_len, then collate_tokens' right-padding with 0) for B decoded clips of different lengths.  Additive: op_abi_version()
+ * stays 10, no existing entry point changed.
+ * src: the clips back to back, clip i at byte desc[i].src_off (a multiple of 16): frames x channels interleaved samples, int16 PCM
+ * (format 0; value s / 32768, stereo (l + r) / 65536, exact) or fp32 (format 1; stereo fl(l + r) * 0.5).  desc: int64 [B][6] per clip
+ * {src_off, frames, channels, format, out_len, part_off}, on the DEVICE; desc_host: the same table in HOST memory (validated here,
+ * sizes the launches).  out_len = max(min(frames, max_len), min_len); part_off = the sum of ceil(frames / 8192) over the clips before
+ * this one (its first 16-byte statistics partial in the workspace).  workspace: 16 bytes per 8192 frames of every clip.
+ * out: [B, T] bf16 (out_dtype 0, round-to-nearest-even) or f32 (1): out[i, t] = (x[t mod min(frames, max_len)] - mean) * rstd for
+ * t < out_len and 0 behind it, with mean and rstd = 1 / sqrt(var + 1e-5) (biased variance) formed in fp64 and rounded to fp32; int16
+ * statistics are integer sums.  Per sample |out - fp64 result| <= 2^-24 (4 |y| + 2 |mean| rstd) for f32.  A clip's values depend on
+ * nothing else in the batch, nor on its row or T; two runs give the same bits (no atomics).
+ * 1 <= frames <= 2^27, channels 1 or 2, 0 <= min_len <= max_len <= 2^27, out_len <= T <= 2^27, B <= 65535; src, out, workspace
+ * 16-byte aligned; else OP_EINVAL before anything is launched.  Two launches: statistics partials, then normalise + pad. */
+int op_audio_normalize_pad(const void* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B, int64_t max_len,
+                           int64_t min_len, void* out, int64_t T, int out_dtype, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,7 @@ SIGNATURES = {
     "op_sim_topk_workspace_bytes": (I64, [I64, I64, I64, I64]),
     "op_sim_topk": (c_int, [P, I64, P, I64, I64, I64, I64, I64, P, P, P, I64, I64, P]),
     "op_image_resize_normalize": (c_int, [P, I64, P, P, I64, P, I64, I64, P, P, P, c_int, P, I64, P]),
+    "op_audio_normalize_pad": (c_int, [P, I64, P, P, I64, I64, I64, P, I64, c_int, P, I64, P]),
 }
 
 
@@ -1081,6 +1082,28 @@ def image_resize_normalize(packed, mean=None, std=None, dtype=torch.bfloat16, de
                                                packed.desc.ctypes.data_as(c_void_p), B, c_void_p(base + packed.coef_off),
                                                packed.coef_count, S, m, sd, ptr(out), _IMAGE_OUT[dtype], ptr(ws), ws.numel(), stream()),
                "op_image_resize_normalize")
+    return out
+
+
+def audio_normalize_pad(packed, dtype=torch.float32, device=None):
+    """[B, T] fp32 / bf16 of an audioprep.PackedClips batch on a device (op_audio_normalize_pad): channel mean, layer norm over each
+    whole clip, crop to max_len, tiling up to min_len, zero padding to T = the longest output, the cast.  The packed host buffer
+    (samples + descriptor table) goes to the device in ONE copy; the statistics partials are a workspace of packed.workspace_bytes."""
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("audio_normalize_pad: dtype must be bfloat16 or float32, got %s" % dtype)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    B, T = len(packed), packed.T
+    out = torch.empty((B, T), dtype=dtype, device=dev)
+    if B == 0:
+        return out
+    with torch.cuda.device(dev):
+        buf = packed.host.to(dev, non_blocking=packed.host.is_pinned())
+        ws = torch.empty(max(packed.workspace_bytes, 16), dtype=torch.uint8, device=dev)
+        base = buf.data_ptr()
+        _check(lib().op_audio_normalize_pad(c_void_p(base), packed.src_bytes, c_void_p(base + packed.desc_off),
+                                            packed.desc.ctypes.data_as(c_void_p), B, packed.max_len, packed.min_len, ptr(out), T,
+                                            DT_BF16 if dtype == torch.bfloat16 else DT_F32, ptr(ws), ws.numel(), stream()),
+               "op_audio_normalize_pad")
     return out
 
 

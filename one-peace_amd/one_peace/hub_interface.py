@@ -2,14 +2,14 @@
 ``from_pretrained(...) -> OnePeaceHubInterface`` with ``extract_{text,image,audio,vl}_features`` (:206-225) and the dtype
 cast of :107-122.  ``process_image`` (:150-168) takes image files, PIL images or decoded uint8 arrays and runs the reference's
 transform (:94-101) -- on a device through the HIP resize kernel (ops.preprocess_images), bit for bit; ``process_text`` takes
-token ids (no BPE) and ``process_audio`` decoded 16 kHz waveforms (no librosa), and do the collation only."""
-import math
+token ids (no BPE) and does the collation only; ``process_audio`` (:170-193) takes 16 kHz WAV files, int16 PCM or float waveforms
+(no librosa, no resampling) and runs layer norm, crop, tiling and padding through ops.preprocess_audio, on a device in
+op_audio_normalize_pad."""
 import os
 from types import SimpleNamespace
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 from ..unify_model_config import one_peace_encoder_config
 from .one_peace_retrieval import OnePeaceRetrievalModel
@@ -111,8 +111,8 @@ class OnePeaceHubInterface:
         tensors (a uint8 [B, H, W, 3] batch works too; arrays never need PIL on a device).  On a device the resize and the
         normalisation run in op_image_resize_normalize (bit-identical to PIL + torchvision); on the CPU PIL does the resize.
         A floating-point tensor is taken as already pre-processed and only moved and cast, as before.
-        Out of scope: JPEG / PNG decoding stays in PIL on the host; process_audio from files (librosa's soxr resampler), BPE for
-        process_text and training-time augmentation (RandomResizedCrop, RandAugment) are not provided."""
+        Out of scope: JPEG / PNG decoding stays in PIL on the host; BPE for process_text, training-time augmentation
+        (RandomResizedCrop, RandAugment) and audio resampling (process_audio takes 16 kHz WAV files) are not provided."""
         from .. import ops
         if torch.is_tensor(image_list) or isinstance(image_list, np.ndarray):
             batch = torch.as_tensor(image_list)
@@ -154,27 +154,27 @@ class OnePeaceHubInterface:
             n = 1 + (n - (k - 1) - 1) // s
         return n
 
-    def process_audio(self, wav_list, sample_rate=16000):
-        """list of 1-D float waveforms @16 kHz -> (src_audios [B, T], audio_padding_masks [B, frames+1]), as
-        hub_interface.py:170-193 after librosa.load: per-waveform layer norm, crop to 15 s, tile up to 1 s, an all-False
-        frame mask of each clip's OWN length, then right-padding of waveforms with 0 and of masks with True."""
-        feats, masks = [], []
-        for w in wav_list:
-            w = torch.as_tensor(w, dtype=torch.float32)
-            w = F.layer_norm(w, w.shape)
-            if w.numel() > sample_rate * 15:
-                w = w[: sample_rate * 15]
-            if w.numel() < sample_rate:
-                w = w.repeat(math.ceil(sample_rate / w.numel()))[:sample_rate]
-            feats.append(w)
-            masks.append(torch.zeros(self._frames(w.numel()) + 1, dtype=torch.bool))
-        T, Fm = max(w.numel() for w in feats), max(m.numel() for m in masks)
-        wavs = torch.zeros(len(feats), T)
-        pad = torch.ones(len(feats), Fm, dtype=torch.bool)
-        for i, (w, m) in enumerate(zip(feats, masks)):
-            wavs[i, : w.numel()] = w
-            pad[i, : m.numel()] = m
-        return self.cast_data_dtype(wavs.to(self.device)), pad.to(self.device)
+    def process_audio(self, audio_list, sample_rate=16000):
+        """hub_interface.py:170-193: (src_audios [B, T], audio_padding_masks [B, frames + 1]) of audio clips.  Items, mixed freely:
+        paths of 16-bit PCM WAV files (audioprep.read_wav), int16 PCM [n] / [n, 2], or float [n] / [n, C] arrays or tensors.  Per
+        clip: mean over the channels, layer norm over the whole clip, crop to 15 s, tiling up to 1 s, an all-False frame mask of the
+        clip's OWN length; then right-padding of the waveforms with 0 and of the masks with True (built on the host).
+        A file whose rate is not `sample_rate` raises ValueError("sample rate: R, need 16000"), as data/base_dataset.py:88-89.
+        Resampling is not provided: the reference's librosa.load(sr=16000) resamples with soxr, which cannot be reproduced (or
+        tested) without librosa / soxr, and the reference's own datasets refuse other rates as well.
+        With device="cpu" this is ops.preprocess_audio's torch route, bit for bit what this method computed for 1-D float
+        waveforms before it took files.  On a GPU device the same inputs go through op_audio_normalize_pad (csrc/audioprep.hip)
+        and may differ from the host route by rounding: each fp32 value is within 2^-24 (4 |y| + 2 |mean| rstd) of the fp64
+        result (torch's own fp32 layer norm was measured at up to 1.84 times that bound on the fixture's clips), before the cast to the
+        hub dtype."""
+        from .. import ops
+        kdt = self.dtype if self.dtype in (torch.bfloat16, torch.float32) else torch.float32
+        wavs, lengths = ops.preprocess_audio(audio_list, sample_rate, 15, 1, dtype=kdt, device=self.device)
+        frames = [self._frames(int(n)) + 1 for n in lengths]
+        pad = torch.ones(len(frames), max(frames, default=0), dtype=torch.bool)
+        for i, f in enumerate(frames):
+            pad[i, :f] = False
+        return self.cast_data_dtype(wavs), pad.to(self.device)
 
     # ---- hipGraph replay of the extract_* calls (MI355X serving path; no reference counterpart) -----------------------
     def enable_graphs(self, on=True):

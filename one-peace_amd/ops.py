@@ -522,6 +522,32 @@ def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, de
 
 
 # --------------------------------------------------------------------------------------------------------------
+# audio pre-processing: base_dataset.py:84-102 / hub_interface.py:170-193 (layer norm, crop, tile, pad) on decoded clips
+# --------------------------------------------------------------------------------------------------------------
+def preprocess_audio(clips, sample_rate=16000, max_seconds=15, min_seconds=1, dtype=torch.float32, device="cpu"):
+    """(wavs [B, T] in `dtype` on `device`, lengths int64 [B] on the host) from audio clips: WAV paths at `sample_rate`, int16 PCM
+    [n] / [n, 2] or float [n] / [n, C] arrays or tensors, mixed freely.  Per clip: mean over the channels, F.layer_norm over the
+    whole clip, crop to sample_rate * max_seconds samples, a clip shorter than sample_rate * min_seconds repeated up to that length;
+    then right-padding with zeros to the longest clip T (`lengths` are the samples before the padding).  On a CUDA device this is
+    op_audio_normalize_pad (hip.audio_normalize_pad: one H2D copy of the staged samples, statistics in integers / fp64, each value
+    within 2^-24 (4 |y| + 2 |mean| rstd) of the fp64 result); on the CPU it is audioprep.postprocess, the reference's own torch
+    arithmetic.  No resampling: a file at another rate is a ValueError."""
+    from . import audioprep
+    arrs = [audioprep.as_clip(c, sample_rate) for c in clips]
+    max_len, min_len = int(sample_rate * max_seconds), int(sample_rate * min_seconds)
+    dev = torch.device(device)
+    if dev.type == "cuda":
+        packed = audioprep.pack_clips(arrs, max_len, min_len)
+        kdt = dtype if dtype in (torch.bfloat16, torch.float32) else torch.float32
+        return hip.audio_normalize_pad(packed, kdt, dev).to(dtype), torch.tensor(packed.lengths, dtype=torch.int64)
+    feats = [audioprep.postprocess(a, sample_rate, max_seconds, min_seconds) for a in arrs]
+    wavs = torch.zeros(len(feats), max([w.numel() for w in feats], default=0))
+    for i, w in enumerate(feats):
+        wavs[i, : w.numel()] = w
+    return wavs.to(device=dev, dtype=dtype), torch.tensor([w.numel() for w in feats], dtype=torch.int64)
+
+
+# --------------------------------------------------------------------------------------------------------------
 # LayerNorm (+ optional fused GELU)
 # --------------------------------------------------------------------------------------------------------------
 class LayerNormFn(torch.autograd.Function):
