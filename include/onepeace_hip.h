@@ -194,7 +194,11 @@ int op_gemm_nt_fp8(const void* A8, int64_t lda, const float* sa, const void* B0,
  * backward then returns one dbias slab per sample.
  * bias_frag (optional): the same image(s) in the fragment-major layout of op_attn_bias_pack; with it (or without any
  * bias) sequences of up to 320 keys run the resident-K/V kernel, which adds the bias with the matrix pipe; a biased call
- * without bias_frag always runs the streaming kernel. */
+ * without bias_frag always runs the streaming kernel.
+ * Preconditions the kernels do not check (tests/test_attention_fp64_gpu.py runs everything else against fp64): S >= 1 (every
+ * row index is clamped to S - 1); bias entries inside [0, S) are FINITE -- keys are masked through key_pad, not with -inf in the
+ * image (the matrix-pipe routes add the bias as a product with a selector, where 0 * inf would turn a whole query block into
+ * NaN); every sample keeps at least one unmasked key (a row with all keys masked has no softmax: NaN, as in the reference). */
 int op_attn_fwd(const void* q, const void* k, const void* v, int64_t ld, const void* bias, int64_t bias_batch_stride,
                 const void* bias_frag, const void* key_pad, void* out, int64_t ldo, float* lse, int64_t lse_ld, int64_t B,
                 int64_t S, int64_t Spad, int64_t heads, int64_t head_dim, float scale, int64_t tune, void* stream);
