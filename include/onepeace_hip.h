@@ -423,6 +423,26 @@ int op_image_resize_normalize(const void* src, int64_t src_bytes, const int64_t*
 int op_audio_normalize_pad(const void* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B, int64_t max_len,
                            int64_t min_len, void* out, int64_t T, int out_dtype, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- classification metrics: average precision per class without a sort or a host copy (csrc/metrics.hip) ---------------------
+ * Replaces the host path of the MAP metric (one_peace/metrics/map.py:35-44: torch.sigmoid(preds).cpu().numpy(), then sklearn's
+ * average_precision_score(targets, preds, average=None): a device-to-host copy of [N, C] floats and one host sort per class).
+ * Additive: op_abi_version() stays 10, no existing entry point changed.
+ * scores: fp32 [N, C], row stride ld_scores elements; targets: uint8 [N, C], row stride ld_targets bytes, non-zero = positive.
+ * ap: fp64 [C]; npos: int32 [C] = P_c, the positives of class c.  With CNT_c(i) = #{j : s_jc >= s_ic} and TP_c(i) = #{j : y_jc != 0 and
+ * s_jc >= s_ic}: ap[c] = 0.0 when P_c = 0 (sklearn 1.7.2's value, which it gives with a warning), else
+ * ap[c] = (sum over the positives i of TP_c(i) / CNT_c(i)) / P_c -- sklearn's sum over thresholds of (recall step) x precision, tied scores
+ * sharing one threshold as in precision_recall_curve.  Order is by fp32 value: -0 equals +0, +-inf are ordinary values; a NaN (refused by
+ * the Python wrapper, as sklearn raises on it) ranks above +inf.  The counts are exact integers; every quotient is a correctly rounded
+ * fp64 division; the terms are summed in an order fixed by the class's own column (64 positives at a time in sample order, a fixed tree
+ * inside the 64, then the groups in sequence) with no floating-point atomics: |ap[c] - exact| <= (P_c + 2) 2^-53, two runs give the same
+ * bits, and a class's result depends on nothing in the other columns, nor on C, ld_scores or ld_targets.
+ * workspace: op_average_precision_workspace_bytes(N, C) = 4 N C + 16 C ceil(N / 64) bytes (ordered keys, target bits and partial sums,
+ * class-major), 16-byte aligned.  1 <= N < 2^31, 1 <= C <= 65535, ld_scores, ld_targets >= C; else OP_EINVAL before anything is
+ * launched.  Three launches: keys and target bits, counts and partial sums (N P_c pair tests per class), the per-class finish. */
+int64_t op_average_precision_workspace_bytes(int64_t N, int64_t C);
+int op_average_precision(const float* scores, int64_t ld_scores, const uint8_t* targets, int64_t ld_targets, int64_t N, int64_t C,
+                         double* ap, int* npos, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,8 @@ SIGNATURES = {
     "op_sim_topk": (c_int, [P, I64, P, I64, I64, I64, I64, I64, P, P, P, I64, I64, P]),
     "op_image_resize_normalize": (c_int, [P, I64, P, P, I64, P, I64, I64, P, P, P, c_int, P, I64, P]),
     "op_audio_normalize_pad": (c_int, [P, I64, P, P, I64, I64, I64, P, I64, c_int, P, I64, P]),
+    "op_average_precision_workspace_bytes": (I64, [I64, I64]),
+    "op_average_precision": (c_int, [P, I64, P, I64, I64, I64, P, P, P, I64, P]),
 }
 
 
@@ -1105,6 +1107,31 @@ def audio_normalize_pad(packed, dtype=torch.float32, device=None):
                                             DT_BF16 if dtype == torch.bfloat16 else DT_F32, ptr(ws), ws.numel(), stream()),
                "op_audio_normalize_pad")
     return out
+
+
+def average_precision(scores, targets):
+    """(ap fp64 [C], npos int32 [C]) of scores fp32 [N, C] and targets uint8 [N, C] (non-zero = positive) on a device
+    (op_average_precision): per class the mean over the positives i of #{positives scoring >= s_i} / #{samples scoring >= s_i}, 0.0 for
+    a class without positives.  Unit column stride, any row stride; the keys, target bits and partial sums are a workspace of
+    op_average_precision_workspace_bytes(N, C)."""
+    assert scores.dtype == torch.float32 and targets.dtype == torch.uint8 and scores.is_cuda and targets.is_cuda, \
+        "average_precision takes fp32 scores and uint8 targets on a CUDA device"
+    assert scores.dim() == 2 and scores.shape == targets.shape, "average_precision: scores and targets [N, C]"
+    N, C = scores.shape
+    if N < 1 or C < 1:
+        raise ValueError("average_precision: need N >= 1 and C >= 1, got [%d, %d]" % (N, C))
+    if scores.stride(1) != 1 or scores.stride(0) < C:
+        scores = scores.contiguous()
+    if targets.stride(1) != 1 or targets.stride(0) < C:
+        targets = targets.contiguous()
+    with torch.cuda.device(scores.device):
+        ap = torch.empty(C, dtype=torch.float64, device=scores.device)
+        npos = torch.empty(C, dtype=torch.int32, device=scores.device)
+        ws_bytes = lib().op_average_precision_workspace_bytes(N, C)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=scores.device)
+        _check(lib().op_average_precision(ptr(scores), scores.stride(0), ptr(targets), targets.stride(0), N, C, ptr(ap), ptr(npos),
+                                          ptr(ws), ws_bytes, stream()), "op_average_precision")
+    return ap, npos
 
 
 def mfma_rate_probe(seconds=1.0, waves_per_cu=8, data="normal", device=None):

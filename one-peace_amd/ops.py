@@ -488,6 +488,58 @@ def similarity_topk(query, gallery, k, splits=None):
 
 
 # --------------------------------------------------------------------------------------------------------------
+# classification: average precision per class (metrics/map.py:35-44 without the host copy, the host sorts and sklearn)
+# --------------------------------------------------------------------------------------------------------------
+def _average_precision_torch(scores, positive):
+    """The formula of op_average_precision in torch: a stable descending sort per class, integer cumulative counts, fp64 quotients.
+    A position's threshold is the LAST position of its run of equal scores: CNT = that position (1-based), TP = the positives up to it."""
+    N, C = scores.shape
+    v, order = torch.sort(scores, dim=0, descending=True, stable=True)
+    y = positive.gather(0, order).long()
+    tp_upto = torch.cumsum(y, dim=0)
+    pos = torch.arange(1, N + 1, device=scores.device).unsqueeze(1).expand(N, C)
+    last = torch.ones(N, C, dtype=torch.bool, device=scores.device)
+    last[:-1] = v[:-1] != v[1:]  # +-inf and -0 / +0 compare as values
+    ends = torch.where(last, pos, torch.full_like(pos, N))
+    cnt = torch.flip(torch.cummin(torch.flip(ends, (0,)), dim=0)[0], (0,))  # the nearest run end at or after each position
+    tp = tp_upto.gather(0, cnt - 1)
+    terms = torch.where(y.bool(), tp.double() / cnt.double(), torch.zeros((), dtype=torch.float64, device=scores.device))
+    npos = y.sum(0)
+    ap = torch.where(npos > 0, terms.sum(0) / npos.clamp(min=1).double(), torch.zeros((), dtype=torch.float64, device=scores.device))
+    return ap, npos
+
+
+def average_precision(scores, targets):
+    """(ap fp64 [C], npos int64 [C]): per class c the average precision of scores[:, c] against the binary targets[:, c], as sklearn's
+    average_precision_score(targets, scores, average=None) defines it -- the mean over the positives i of
+    #{positives scoring >= s_i} / #{samples scoring >= s_i}, tied scores sharing one threshold; 0.0 for a class without positives.
+    scores fp32 / bf16 / fp16 (cast to fp32 first), targets bool / integer (non-zero = positive) / float (0 or 1).  ValueError, as
+    sklearn raises: different shapes, a NaN score, a float target other than 0 or 1.  CUDA inputs run op_average_precision
+    (hip.average_precision: the [N, C] scores never leave the device; one sync for the checks); anything else the torch statement of
+    the same formula."""
+    if scores.dim() != 2 or tuple(scores.shape) != tuple(targets.shape):
+        raise ValueError("average_precision: scores and targets must be [N, C] of one shape, got %s and %s" % (
+            tuple(scores.shape), tuple(targets.shape)))
+    if scores.shape[0] < 1 or scores.shape[1] < 1:
+        raise ValueError("average_precision: need N >= 1 and C >= 1, got %s" % (tuple(scores.shape),))
+    if not scores.is_floating_point():
+        raise ValueError("average_precision: scores must be floating point, got %s" % scores.dtype)
+    targets = targets.to(scores.device)
+    scores = scores.float()
+    bad_target = ((targets != 0) & (targets != 1)).any() if targets.is_floating_point() else torch.zeros((), dtype=torch.bool, device=scores.device)
+    has_nan, bad_target = torch.stack([torch.isnan(scores).any(), bad_target]).tolist()
+    if has_nan:
+        raise ValueError("average_precision: scores contain NaN")
+    if bad_target:
+        raise ValueError("average_precision: float targets must be 0 or 1")
+    positive = targets != 0
+    if scores.is_cuda:
+        ap, npos = hip.average_precision(scores, positive.to(torch.uint8))
+        return ap, npos.long()
+    return _average_precision_torch(scores, positive)
+
+
+# --------------------------------------------------------------------------------------------------------------
 # image pre-processing: hub_interface.py:94-101 (Resize((S, S), BICUBIC), ToTensor, Normalize) on decoded images
 # --------------------------------------------------------------------------------------------------------------
 def _is_pil(im):
