@@ -328,7 +328,9 @@ int op_infonce_rows(float* sim, int64_t rows, int64_t n, int64_t ld, int64_t tar
 /* ---- optimiser -------------------------------------------------------------------------------------------------------
  * One AdamW update over a flat bf16 parameter range, the rule of one_peace/optim/adam.py:186-253 (what the reference
  * runs without apex): fp32 moments, decoupled decay before the update, eps added to sqrt(v).  g is multiplied by
- * grad_scale inside the kernel (1/world after a SUM all-reduce).  numel % 8 == 0, step >= 1. */
+ * grad_scale inside the kernel (1/world after a SUM all-reduce).  numel % 8 == 0, step >= 1.  With grad_sqnorm and clip_norm > 0
+ * the gradient is also multiplied by clamp(clip_norm / (|grad_scale| sqrt(*grad_sqnorm) + 1e-6), max = 1); a NaN sum of squares
+ * makes every parameter and moment of the range NaN (nothing is stepped with the unclipped gradient), +inf gives coefficient 0. */
 int op_adamw_step(void* p, const void* g, float* m, float* v, int64_t numel, float lr, float beta1, float beta2, float eps,
                   float weight_decay, int64_t step, float grad_scale, const float* grad_sqnorm, float clip_norm,
                   void* stream);

@@ -438,16 +438,28 @@ __global__ __launch_bounds__(256) void infonce_rows_kernel(float* __restrict__ s
 // AdamW as the reference does it (one_peace/optim/adam.py:186-253): fp32 math on bf16 params, decoupled
 // decay applied to the parameter before the Adam update, eps added to sqrt(v).
 // Algorithmic bytes: 22 B/param (p r+w 4, g r 2, m and v r+w 16).
+// Non-finite gradients with clipping on: a NaN anywhere in the gradient buffer makes the norm NaN, the clip coefficient NaN
+// (fminf would have returned 1 and stepped every other parameter with the unclipped gradient) and with it EVERY parameter and
+// moment of the step, as optim.TorchAdamW's clamp does; an infinite norm gives coefficient 0, and only the infinite elements
+// turn NaN.  The reference raises before its optimiser step instead (trainer.py:830-837): the norm is what a loop checks.
 // ------------------------------------------------------------------------------------------------------------
+// grad_scale times the reference's clip coefficient (fairseq/utils.py:393-397: clamp(max_norm / (norm + 1e-6), max=1), norm =
+// |grad_scale| sqrt(sqnorm)).  torch's clamp, not fminf: a NaN coefficient stays NaN.  Formed in fp64 and rounded ONCE: every
+// gradient is multiplied by this number and v by its square, so the four fp32 roundings of sqrtf, the sum, the quotient and the
+// product reached v doubled (measured: 1.19 x the bound tests/adamw_ref.py derives for v).  A handful of fp64 operations per thread.
+__device__ __forceinline__ float clipped_grad_scale(float grad_scale, const float* __restrict__ sqnorm, float clip_norm) {
+  if (sqnorm == nullptr || !(clip_norm > 0.f)) return grad_scale;
+  const double norm = fabs((double)grad_scale) * sqrt((double)*sqnorm);
+  const double c = (double)clip_norm / (norm + 1e-6);
+  return (c < 1.0 || c != c) ? (float)((double)grad_scale * c) : grad_scale;
+}
+
 __global__ __launch_bounds__(256) void adamw_kernel(bf16_t* __restrict__ p, const bf16_t* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v, int64_t n8,
                                                     float beta1, float beta2, float eps, float step_size,
                                                     float decay_mul, float grad_scale, const float* __restrict__ sqnorm,
                                                     float clip_norm) {
-  if (sqnorm != nullptr && clip_norm > 0.f) {  // fairseq/utils.py:393-397: clip_coef = clamp(max_norm / (norm + 1e-6), max=1)
-    const float norm = fabsf(grad_scale) * sqrtf(*sqnorm);
-    grad_scale *= fminf(1.0f, clip_norm / (norm + 1e-6f));
-  }
+  grad_scale = clipped_grad_scale(grad_scale, sqnorm, clip_norm);
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
     float pv[8], gv[8], mv[8], vv[8];
     Vec8<bf16_t>::load(p + i * 8, pv);
@@ -488,10 +500,7 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(bf16_t* __restrict__ 
     s_decay[i] = 1.f - wd[i] * lr_g;       // p <- p - wd * lr_g * p, before the Adam update (adam.py:243-246)
   }
   __syncthreads();
-  if (sqnorm != nullptr && clip_norm > 0.f) {
-    const float norm = fabsf(grad_scale) * sqrtf(*sqnorm);
-    grad_scale *= fminf(1.0f, clip_norm / (norm + 1e-6f));
-  }
+  grad_scale = clipped_grad_scale(grad_scale, sqnorm, clip_norm);
   int grp = 0;
   int64_t lo = 0, hi = s_end[0];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {

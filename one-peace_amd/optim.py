@@ -72,7 +72,11 @@ class FusedAdamW:
         """grad_scale multiplies the gradient inside the kernel (1/world_size after a SUM all-reduce, trainer.py:917-923).
         clip_norm > 0: the reference's global-norm clipping (trainer.py:929 -> fairseq/utils.py:349-397) -- the norm is
         one extra pass over the flat gradient buffer, the clip coefficient is derived on the device inside the update
-        kernel.  Returns the (unclipped, scaled) gradient norm as a device scalar when clipping is on."""
+        kernel.  Returns the (unclipped, scaled) gradient norm as a device scalar when clipping is on.
+        A non-finite gradient norm makes the whole step non-finite: with a NaN anywhere in the gradients every parameter and both
+        moments come out NaN (``TorchAdamW`` does the same), nothing is stepped quietly with the unclipped gradient.  The returned
+        norm is what a training loop should check before it steps, as the reference does (trainer.py:830-837 raises
+        FloatingPointError); without clipping no norm is computed and a NaN gradient reaches its own element only."""
         self.step_count += 1
         f = self.flat
         sq = hip.sqnorm(f.grads) if clip_norm > 0 else None
