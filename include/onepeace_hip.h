@@ -445,6 +445,44 @@ int64_t op_average_precision_workspace_bytes(int64_t N, int64_t C);
 int op_average_precision(const float* scores, int64_t ld_scores, const uint8_t* targets, int64_t ld_targets, int64_t N, int64_t C,
                          double* ap, int* npos, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- fine-tuning losses: loss, logged counter and gradient in one pass over the logits (csrc/losses.hip) -------------------------
+ * Additive: op_abi_version() stays 10, no existing entry point changed.
+ * op_row_loss: logits [B, C], bf16 (dtype 0) or fp32 (dtype 1), row stride ld >= C elements.  Per row it writes row_loss fp32 [B],
+ * row_correct fp32 [B] and, when dlogits is non-null, dlogits fp32 [B, C] (dense) = gscale * d row_loss / d logits.  When sums is non-null
+ * a second launch writes sums[0] = sum of row_loss, sums[1] = sum of row_correct, in a fixed order.  fp32 math, the row maximum
+ * subtracted before every exponential; the row is read from memory once (staged in LDS up to 4096 columns; later columns are read again
+ * from the caches); no floating-point atomics: two runs give the same bits.  mode:
+ *   0 hard   one_peace/criterions/classify_loss.py:62-64: F.cross_entropy(logits, targets, label_smoothing = eps, reduction = 'sum')
+ *            and logits.argmax(1).eq(targets).  targets int64 [B].  row_loss = (1 - eps) nll + (eps / C) sum_c -logp_c (torch's
+ *            smoothing: over C, not the C - 1 of op_infonce_rows); row_correct = (argmax == target), the lowest index winning a tie.
+ *            Target -100 (ignore_index): loss 0, gradient 0, correct 0.  Any other target outside [0, C): loss NaN, gradient 0, correct 0;
+ *            nothing is read at such an index.
+ *   1 soft   classify_loss.py:56-60: utils.log_softmax, (-targets * log_probs).sum(), (log_probs.exp() * targets).sum().  targets [B, C]
+ *            bf16 / fp32 (target_dtype), row stride ld_targets; they need not sum to 1.  row_loss = sum_c -t_c logp_c,
+ *            row_correct = sum_c p_c t_c, gradient p_c sum_k t_k - t_c.
+ *   2 multi  classify_loss.py:51-54: F.binary_cross_entropy_with_logits(logits, targets, reduction = 'sum') and
+ *            targets.gather(1, logits.argmax(1, keepdim = True)).  row_loss = sum_c max(x, 0) - x t + log1p(exp(-|x|)), gradient
+ *            sigmoid(x) - t, row_correct = t[argmax x].
+ *   3 hinge  one_peace/criterions/hinge_loss.py:49-53: rows of C = num_choices logits, targets int64 [B] (outside [0, C): as in mode 0,
+ *            without an ignore_index).  row_loss = sum_k max(0, (margin + x_k) - x_target), the k = target term included; where the
+ *            argument is exactly 0 the subgradient is 0.5, as torch.max(tensor, tensor) gives; row_correct = (argmax == target).  The
+ *            reference hard-codes `1 +` and ignores its own margin option; here margin is honoured (equal at the default 1.0).
+ * A NaN logit makes that row's loss NaN and ranks as the row's arg-max, as in torch.  label_smoothing is read in mode 0, margin in mode 3,
+ * target_dtype and ld_targets in modes 1 and 2.  OP_EINVAL before any launch: null or misaligned pointers, B < 0, C < 1, ld < C,
+ * ld_targets < C, unknown mode or dtype, label_smoothing outside [0, 1).  B == 0 returns without a launch. */
+int op_row_loss(const void* logits, int dtype, int64_t ld, const void* targets, int target_dtype, int64_t ld_targets, int64_t B, int64_t C,
+                int mode, float label_smoothing, float margin, float gscale, float* row_loss, float* row_correct, float* dlogits,
+                float* sums, void* stream);
+/* one_peace/criterions/refcoco_loss.py:36-46 with B = nsentences: logits [B, 4] bf16 / fp32 (dense), targets fp32 [B, 4] (x1, y1, x2, y2).
+ * o = sigmoid(logits); out[0] = sum |o - t| / B + the mean over the valid rows (o_x1 < o_x2 and o_y1 < o_y2) of 1 - GIoU(o_i, t_i),
+ * out[1] = the number of valid rows.  GIoU by the formulae of torchvision.ops.generalized_box_iou (clamped intersection and enclosing
+ * extents, iou - (enclosing - union) / enclosing), the diagonal only: no [B, B] matrix.  dlogits (may be null) fp32 [B, 4] =
+ * gscale * d out[0] / d logits through the sigmoid, with torch's subgradients: sign(0) = 0, 1/2 to each side of a tied max / min, the
+ * clamp passing the gradient at 0.  With no valid row out[0] is NaN (the mean of an empty tensor) and the gradient is that of the L1
+ * term.  One workgroup: the valid rows are counted, in a fixed order, before anything is divided.  B < 2^24; B == 0 returns without
+ * a launch. */
+int op_box_loss(const void* logits, int dtype, const float* targets, int64_t B, float gscale, float* out, float* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,8 @@ SIGNATURES = {
     "op_audio_normalize_pad": (c_int, [P, I64, P, P, I64, I64, I64, P, I64, c_int, P, I64, P]),
     "op_average_precision_workspace_bytes": (I64, [I64, I64]),
     "op_average_precision": (c_int, [P, I64, P, I64, I64, I64, P, P, P, I64, P]),
+    "op_row_loss": (c_int, [P, c_int, I64, P, c_int, I64, I64, I64, c_int, c_float, c_float, c_float, P, P, P, P, P]),
+    "op_box_loss": (c_int, [P, c_int, P, I64, c_float, P, P, P]),
 }
 
 
@@ -1132,6 +1134,48 @@ def average_precision(scores, targets):
         _check(lib().op_average_precision(ptr(scores), scores.stride(0), ptr(targets), targets.stride(0), N, C, ptr(ap), ptr(npos),
                                           ptr(ws), ws_bytes, stream()), "op_average_precision")
     return ap, npos
+
+
+ROW_LOSS_HARD, ROW_LOSS_SOFT, ROW_LOSS_MULTI, ROW_LOSS_HINGE = 0, 1, 2, 3
+
+
+def row_loss(logits, targets, mode, label_smoothing=0.0, margin=1.0, gscale=1.0, write_grad=True):
+    """op_row_loss on logits [B, C] (bf16 / fp32, unit column stride; a column slice of a wider matrix is fine).  targets: int64 [B] in
+    the hard and hinge modes, bf16 / fp32 [B, C] in the soft and multi-label modes.  Returns (sums fp32 [2] = (sum of the row losses,
+    sum of the row counters), row_loss fp32 [B], row_correct fp32 [B], dlogits fp32 [B, C] or None)."""
+    assert logits.is_cuda and logits.dim() == 2 and logits.stride(1) == 1, "row_loss takes CUDA logits [B, C] with unit column stride"
+    B, C = logits.shape
+    dense = mode in (ROW_LOSS_SOFT, ROW_LOSS_MULTI)
+    if dense:
+        assert targets.is_cuda and tuple(targets.shape) == (B, C) and targets.stride(1) == 1, "row_loss: targets [B, C], unit column stride"
+        tdt, ldt = _dt(targets), targets.stride(0)
+    else:
+        _req(targets, "targets", torch.int64)
+        assert tuple(targets.shape) == (B,), "row_loss: targets [B]"
+        tdt, ldt = 0, 0
+    dev = logits.device
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    correct = torch.empty(B, dtype=torch.float32, device=dev)
+    dlogits = torch.empty(B, C, dtype=torch.float32, device=dev) if write_grad else None
+    sums = torch.zeros(2, dtype=torch.float32, device=dev) if B == 0 else torch.empty(2, dtype=torch.float32, device=dev)
+    _check(lib().op_row_loss(ptr(logits), _dt(logits), logits.stride(0) if B > 1 else max(C, logits.stride(0)), ptr(targets), tdt,
+                             ldt if B > 1 else max(C, ldt), B, C, mode, label_smoothing, margin, gscale, ptr(loss), ptr(correct),
+                             ptr(dlogits), ptr(sums), stream()), "op_row_loss")
+    return sums, loss, correct, dlogits
+
+
+def box_loss(logits, targets, gscale=1.0, write_grad=True):
+    """op_box_loss on contiguous logits [B, 4] (bf16 / fp32) and fp32 targets [B, 4].  Returns (out fp32 [2] = (loss, valid rows),
+    dlogits fp32 [B, 4] or None)."""
+    _req(logits, "logits")
+    _req(targets, "targets", torch.float32)
+    assert logits.dim() == 2 and logits.shape[1] == 4 and tuple(targets.shape) == tuple(logits.shape), "box_loss: logits, targets [B, 4]"
+    B = logits.shape[0]
+    out = torch.full((2,), float("nan"), dtype=torch.float32, device=logits.device) if B == 0 else torch.empty(
+        2, dtype=torch.float32, device=logits.device)
+    dlogits = torch.empty(B, 4, dtype=torch.float32, device=logits.device) if write_grad else None
+    _check(lib().op_box_loss(ptr(logits), _dt(logits), ptr(targets), B, gscale, ptr(out), ptr(dlogits), stream()), "op_box_loss")
+    return out, dlogits
 
 
 def mfma_rate_probe(seconds=1.0, waves_per_cu=8, data="normal", device=None):

@@ -14,6 +14,7 @@ import os
 import weakref
 
 import torch
+import torch.nn.functional as F
 
 from . import hip
 
@@ -1662,3 +1663,142 @@ class DclFn(torch.autograd.Function):
 
 def dcl_loss(student, teacher, scale, label_smoothing=0.0, block=4096):
     return DclFn.apply(student, teacher, scale, label_smoothing, block)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# fine-tuning losses (one_peace/criterions/{classify_loss,hinge_loss,refcoco_loss}.py): loss, logged counter and gradient from one
+# kernel pass (csrc/losses.hip) instead of a chain of small launches
+# --------------------------------------------------------------------------------------------------------------
+def loss_hip_eligible(logits):
+    """op_row_loss / op_box_loss take bf16 and fp32 CUDA logits [B, C]; anything else runs the reference's torch formulae."""
+    return logits.is_cuda and logits.dim() == 2 and logits.dtype in (torch.bfloat16, torch.float32)
+
+
+class RowLossFn(torch.autograd.Function):
+    """(sum of the row losses, sum of the row counters) of op_row_loss, both fp32 0-d; the fp32 gradient is formed in the same pass and
+    kept for backward.  The sum over the rows is the kernel's fixed-order fp32 sum."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, mode, label_smoothing, margin):
+        x = logits.detach()
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        sums, _, _, dlogits = hip.row_loss(x, targets, mode, label_smoothing, margin, write_grad=ctx.needs_input_grad[0])
+        if dlogits is not None:
+            ctx.save_for_backward(dlogits)
+        ctx.dtype = logits.dtype
+        loss, counter = sums[0], sums[1]
+        ctx.mark_non_differentiable(counter)  # logged, as under the reference's no_grad
+        return loss, counter
+
+    @staticmethod
+    def backward(ctx, g, _gc):
+        (dlogits,) = ctx.saved_tensors
+        return (dlogits * g.float()).to(ctx.dtype), None, None, None, None
+
+
+def _dense_targets(targets, logits):
+    targets = targets.to(logits.device)
+    if targets.dtype not in (torch.bfloat16, torch.float32):
+        targets = targets.float()
+    return targets if targets.stride(1) == 1 else targets.contiguous()
+
+
+def classify_loss(logits, targets, use_multi_label=False, label_smoothing=0.0):
+    """(loss_sum, n_correct) of classify_loss.py:51-64 for logits [B, C].  use_multi_label: binary cross-entropy with logits against
+    targets [B, C], n_correct = the targets at the arg-max.  Else targets [B, C] are soft labels (they need not sum to 1):
+    sum -t logp, n_correct = sum p t; targets [B] int64 are classes: F.cross_entropy with torch's label smoothing (eps / C on every
+    class) and ignore_index -100, n_correct = the arg-max hits.  CUDA logits in bf16 / fp32 run op_row_loss (fp32 loss and counter,
+    run-to-run identical; a class outside [0, C) other than -100 gives a NaN loss where torch raises a device assert); anything else the
+    reference's own torch calls."""
+    if loss_hip_eligible(logits):
+        if use_multi_label or targets.dim() == 2:
+            if tuple(targets.shape) != tuple(logits.shape):
+                raise ValueError("classify_loss: targets %s do not match logits %s" % (tuple(targets.shape), tuple(logits.shape)))
+            mode = hip.ROW_LOSS_MULTI if use_multi_label else hip.ROW_LOSS_SOFT
+            return RowLossFn.apply(logits, _dense_targets(targets, logits), mode, 0.0, 1.0)
+        if tuple(targets.shape) != (logits.shape[0],):
+            raise ValueError("classify_loss: targets %s do not match logits %s" % (tuple(targets.shape), tuple(logits.shape)))
+        return RowLossFn.apply(logits, targets.to(logits.device, torch.int64).contiguous(), hip.ROW_LOSS_HARD, float(label_smoothing), 1.0)
+    if use_multi_label:
+        loss = F.binary_cross_entropy_with_logits(logits, targets, reduction="sum")
+        with torch.no_grad():
+            n_correct = targets.gather(1, logits.argmax(1, keepdim=True)).sum()
+    elif targets.dim() == 2:
+        log_probs = F.log_softmax(logits, dim=-1, dtype=torch.float32)  # fairseq's utils.log_softmax
+        loss = (-targets * log_probs).sum()
+        with torch.no_grad():
+            n_correct = (log_probs.exp() * targets).sum()
+    else:
+        loss = F.cross_entropy(logits, targets, label_smoothing=label_smoothing, reduction="sum")
+        with torch.no_grad():
+            n_correct = logits.argmax(1).eq(targets).sum()
+    return loss, n_correct
+
+
+def hinge_loss(logits, targets, margin=1.0):
+    """(loss_sum, n_correct) of hinge_loss.py:51-53 for logits [B, num_choices] and int64 targets [B]:
+    sum max(0, margin + logits - logits[target]) over every choice, the target's own included, and the arg-max hits.  The reference
+    hard-codes `1 +` and ignores its own `margin` option; here margin is honoured, which equals the reference at the default 1.0.
+    CUDA logits in bf16 / fp32 run op_row_loss; anything else the reference's torch calls."""
+    if loss_hip_eligible(logits):
+        if tuple(targets.shape) != (logits.shape[0],):
+            raise ValueError("hinge_loss: targets %s do not match logits %s" % (tuple(targets.shape), tuple(logits.shape)))
+        return RowLossFn.apply(logits, targets.to(logits.device, torch.int64).contiguous(), hip.ROW_LOSS_HINGE, 0.0, float(margin))
+    positive_logits = logits.gather(1, targets.unsqueeze(1))
+    loss = torch.max(torch.tensor(0.0).to(logits.device), margin + logits - positive_logits).sum()
+    n_correct = logits.argmax(1).eq(targets).sum()
+    return loss, n_correct
+
+
+def giou_diagonal(boxes1, boxes2):
+    """The diagonal of torchvision.ops.generalized_box_iou(boxes1, boxes2), boxes [N, 4] as (x1, y1, x2, y2): the published formulae
+    (clamped intersection and enclosing extents, iou - (enclosing - union) / enclosing) for the pairs (i, i) only."""
+    if boxes1.dtype not in (torch.float32, torch.float64):
+        boxes1, boxes2 = boxes1.float(), boxes2.float()  # torchvision's _upcast
+    area1 = (boxes1[:, 2] - boxes1[:, 0]) * (boxes1[:, 3] - boxes1[:, 1])
+    area2 = (boxes2[:, 2] - boxes2[:, 0]) * (boxes2[:, 3] - boxes2[:, 1])
+    wh = (torch.min(boxes1[:, 2:], boxes2[:, 2:]) - torch.max(boxes1[:, :2], boxes2[:, :2])).clamp(min=0)
+    inter = wh[:, 0] * wh[:, 1]
+    union = area1 + area2 - inter
+    iou = inter / union
+    whi = (torch.max(boxes1[:, 2:], boxes2[:, 2:]) - torch.min(boxes1[:, :2], boxes2[:, :2])).clamp(min=0)
+    areai = whi[:, 0] * whi[:, 1]
+    return iou - (areai - union) / areai
+
+
+def box_loss_torch(logits, targets, nsentences=None):
+    """refcoco_loss.py:36-46 in torch, the [B, B] GIoU matrix replaced by its diagonal."""
+    output_coords = logits.sigmoid()
+    loss = F.l1_loss(output_coords, targets, reduction="sum")
+    loss = loss / (logits.shape[0] if nsentences is None else nsentences)
+    valid_indices = (output_coords[:, :2] < output_coords[:, 2:]).all(1)
+    ious = giou_diagonal(output_coords[valid_indices], targets[valid_indices])
+    return loss + (1 - ious).mean()
+
+
+class BoxLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets):
+        out, dlogits = hip.box_loss(logits.detach().contiguous(), targets, write_grad=ctx.needs_input_grad[0])
+        if dlogits is not None:
+            ctx.save_for_backward(dlogits)
+        ctx.dtype = logits.dtype
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlogits,) = ctx.saved_tensors
+        return (dlogits * g.float()).to(ctx.dtype), None
+
+
+def box_loss(logits, targets):
+    """The loss of refcoco_loss.py:36-46 for box logits [B, 4] and target boxes [B, 4] as (x1, y1, x2, y2) in [0, 1]:
+    sum |sigmoid(logits) - targets| / B + the mean of 1 - GIoU over the rows whose predicted box has x1 < x2 and y1 < y2 (NaN when
+    there is none, as the mean of an empty tensor).  CUDA logits in bf16 / fp32 run op_box_loss (fp32 loss); anything else the torch
+    statement.  No [B, B] GIoU matrix and no torchvision either way."""
+    if logits.dim() != 2 or logits.shape[1] != 4 or tuple(targets.shape) != tuple(logits.shape):
+        raise ValueError("box_loss: logits and targets must be [B, 4], got %s and %s" % (tuple(logits.shape), tuple(targets.shape)))
+    if loss_hip_eligible(logits):
+        return BoxLossFn.apply(logits, targets.to(logits.device, torch.float32).contiguous())
+    return box_loss_torch(logits, targets)
