@@ -67,7 +67,8 @@ int op_layernorm_bwd(const void* dy, const void* x, const void* w, const void* b
  *             or none) receive the two pre-activations for the backward pass
  *          3: C(bf16) = resid + rowscale[m / rows_per_sample] * gamma[n] * (acc + bias[n]); gamma/rowscale NULL = 1;
  *             resid may alias C; h0 (optional) receives acc + bias.
- * K % 64 == 0, N % 8 == 0, lda/ldb % 8 == 0 (host pads otherwise: one-peace_amd/ops.py gemm_any).
+ * K % 64 == 0, N % 8 == 0, lda/ldb % 8 == 0 (host pads otherwise: one-peace_amd/ops.py gemm_any); ldc % 8 == 0 for the bf16 outputs
+ * (C, h0, h1 share it), ldc % 4 == 0 for epilogue 1: rows are stored in 16-byte pieces.  Anything else returns -22.
  * workspace (optional fp32 scratch): lets the launch planner split K over several workgroups for bias-free epilogue-0
  * launches with few output tiles and a long K (weight gradients); tile size (128^2 / 256^2) and the split are chosen
  * from a wave-quantisation model. */
@@ -82,7 +83,7 @@ int op_gemm_nt(const void* A, int64_t lda, const void* B0, const void* B1, const
  * branch keeps go straight back to their places (transformer_layer.py:78-88 without the products by zero). */
 /* C[M,N] (bf16) = A^T B with A [K,M] (lda), B [K,N] (ldb) row-major bf16: the weight-gradient GEMM dW = dy^T x of
  * nn.Linear (autograd of components.py:29-34 users) straight from the activation matrices (transpose-read fragments,
- * no transposed copies).  K % 64 == 0, M/N/lda/ldb % 8 == 0, else returns -95 (use op_transpose + op_gemm_nt).
+ * no transposed copies).  K % 64 == 0, M/N/lda/ldb/ldc % 8 == 0, else returns -95 (use op_transpose + op_gemm_nt).
  * accumulate != 0: C += A^T B.  workspace: optional fp32 scratch enabling split-K. */
 int op_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                int accumulate, void* workspace, int64_t workspace_bytes, int64_t tune, void* stream);
@@ -100,7 +101,8 @@ int op_gemm_nt_grouped(int64_t nprob, const void* const* A, const int64_t* M, in
                        int64_t resid_rows_total, void* stream); /* resid_rows: nullable HOST array of nprob DEVICE tables, see op_gemm_nt */
 /* (ABI 7) `batch` equally shaped products  C_z[M,N] = A_z[M,K] W_z[N,K]^T (+ bias_z[N])  with operands at constant element strides as ONE
  * launch (blockIdx.z = z; 128 x 128 tiles, no split-K): the per-group GEMMs of the audio adapter's grouped positional Conv1d over
- * strided patch views (one_peace/models/adapter/audio.py:57-84; each group alone fills half the chip).  bias nullable. */
+ * strided patch views (one_peace/models/adapter/audio.py:57-84; each group alone fills half the chip).  bias nullable.  K % 64 == 0,
+ * N / lda / ldb / ldc and every stride % 8 == 0. */
 int op_gemm_nt_batched(const void* A, int64_t lda, int64_t stride_a, const void* W, int64_t ldb, int64_t stride_b, const void* bias,
                        int64_t stride_bias, void* C, int64_t ldc, int64_t stride_c, int64_t M, int64_t N, int64_t K, int64_t batch,
                        void* stream);

@@ -2385,8 +2385,13 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* B0, const void* 
   }
   OP_CHECK_ARG(M >= 0 && N > 0 && K > 0, "gemm_nt: bad sizes M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
   OP_CHECK_ARG(K % BK == 0, "gemm_nt: K=%lld must be a multiple of %d (pad on the host)", (long long)K, BK);  // => even number of 32-deep stages
-  OP_CHECK_ARG(N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0, "gemm_nt: N, lda, ldb must be multiples of 8");
+  OP_CHECK_ARG(N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0, "gemm_nt: N, lda, ldb must be multiples of 8");
   OP_CHECK_ARG(epilogue >= 0 && epilogue <= 3, "gemm_nt: bad epilogue %d", epilogue);
+  // every output row is written in 16-byte pieces (Vec8 / f32x4 / buffer_store_dwordx4 at m * ldc + 8 j): 4 floats or 8 bf16.  A bf16
+  // output (C, and h0 / h1, which share ldc) at ldc % 8 == 4 would put every odd row 8 bytes off -- a misaligned vector access in every
+  // kernel, and in-place reads of resid = C with it.
+  OP_CHECK_ARG(ldc % (epilogue == EPI_F32 ? 4 : 8) == 0, "gemm_nt: ldc=%lld must be a multiple of %d (rows are stored in 16-byte pieces)",
+               (long long)ldc, epilogue == EPI_F32 ? 4 : 8);
   if (M == 0) return OP_OK;
   GemmArgs a;
   a.A = (const bf16_t*)A; a.lda = lda;
@@ -2417,8 +2422,9 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* B0, const void* 
   const double flops = 2.0 * (double)M * (double)N * (double)K * (epilogue == EPI_GEGLU ? 2.0 : 1.0);
   const bool seg_ok = epilogue == EPI_GEGLU || a.n_seg >= (int)N || a.n_seg % 256 == 0;
   const bool off32_ok = (M * lda < ((int64_t)1 << 30)) && (N * ldb < ((int64_t)1 << 30));
-  const NtDecision dec = decide_nt(M, N, K, epilogue, bias0 != nullptr, seg_ok, off32_ok, a.n_seg % 8 == 0 && ldc % 8 == 0,
-                                   workspace != nullptr, workspace_bytes, allow_tail_split, T);
+  // (ldc % 8 == 0 holds for every epilogue that can fold: checked above)
+  const NtDecision dec = decide_nt(M, N, K, epilogue, bias0 != nullptr, seg_ok, off32_ok, a.n_seg % 8 == 0, workspace != nullptr,
+                                   workspace_bytes, allow_tail_split, T);
   const GemmPlan plan = dec.plan;
   const bool fold_epi = dec.fold_epi;
   if (dec.tail_split) {
@@ -2498,15 +2504,15 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* B0, const void* 
 // `batch` equally shaped products  C_z[M,N] = A_z[M,K] W_z[N,K]^T (+ bias_z[N])  whose operands lie at constant element strides
 // (stride_* between consecutive problems; bias / stride_bias optional): ONE launch of the 128 x 128 kernel with blockIdx.z = z, no
 // split-K.  The per-group GEMMs of a grouped Conv1d over strided patch views (adapter/audio.py:57-84, GroupedConv1dSameFn): each of them
-// alone fills half the chip.  Rules as op_gemm_nt's plain epilogue (K % 64 == 0, N % 8 == 0, lda / ldb % 8 == 0, ldc % 4 == 0).
+// alone fills half the chip.  Rules as op_gemm_nt's plain epilogue (K % 64 == 0, N % 8 == 0, lda / ldb / ldc % 8 == 0).
 int op_gemm_nt_batched(const void* A, int64_t lda, int64_t stride_a, const void* W, int64_t ldb, int64_t stride_b, const void* bias,
                        int64_t stride_bias, void* C, int64_t ldc, int64_t stride_c, int64_t M, int64_t N, int64_t K, int64_t batch,
                        void* stream) {
   OP_CHECK_ARG(A && W && C, "gemm_nt_batched: null A/W/C");
   OP_CHECK_ARG(M >= 0 && N > 0 && K > 0 && batch >= 1 && batch <= 65535, "gemm_nt_batched: bad sizes M=%lld N=%lld K=%lld batch=%lld", (long long)M,
                (long long)N, (long long)K, (long long)batch);
-  OP_CHECK_ARG(K % BK == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 4 == 0, "gemm_nt_batched: K %% 64, N %% 8, lda / ldb %% 8, ldc %% 4");
-  OP_CHECK_ARG(stride_a % 8 == 0 && stride_b % 8 == 0 && stride_c % 4 == 0 && stride_bias % 8 == 0, "gemm_nt_batched: strides must keep 16-byte alignment");
+  OP_CHECK_ARG(K % BK == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldc % 8 == 0, "gemm_nt_batched: K %% 64, N %% 8, lda / ldb / ldc %% 8");
+  OP_CHECK_ARG(stride_a % 8 == 0 && stride_b % 8 == 0 && stride_c % 8 == 0 && stride_bias % 8 == 0, "gemm_nt_batched: strides must keep 16-byte alignment");
   if (M == 0) return OP_OK;
   GemmArgs a;
   memset(&a, 0, sizeof(a));
@@ -2631,17 +2637,17 @@ int op_gemm_nt_grouped(int64_t nprob, const void* const* A, const int64_t* M, in
 
 // C[M,N] (bf16, ldc) = A^T B with A [K, M] (lda) and B [K, N] (ldb) both row-major bf16: the weight-gradient GEMM
 // dW[out,in] = dy[tokens,out]^T x[tokens,in] (autograd of nn.Linear) without transposed operand copies.
-// Requirements: K % 64 == 0, M % 8 == 0, N % 8 == 0, lda/ldb % 8 == 0.  Returns OP_ENOTSUP (-95) when the shape does not
+// Requirements: K % 64 == 0, M % 8 == 0, N % 8 == 0, lda/ldb/ldc % 8 == 0.  Returns OP_ENOTSUP (-95) when the shape does not
 // qualify (the caller then uses op_transpose + op_gemm_nt).  accumulate != 0: C += A^T B (gradient accumulation into a
 // pre-existing buffer).  workspace: optional fp32 scratch enabling split-K.
 int op_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
                int accumulate, void* workspace, int64_t workspace_bytes, int64_t tune, void* stream) {
   const GemmTune T = decode_tune(tune);
   OP_CHECK_ARG(A && B && C, "gemm_tn: null pointer");
-  if (K % 64 != 0 || M % 8 != 0 || N % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0 || M < 8 || N < 8 ||
+  if (K % 64 != 0 || M % 8 != 0 || N % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0 || ldc % 8 != 0 || M < 8 || N < 8 ||
       31 * lda + M >= ((int64_t)1 << 30) || 31 * ldb + N >= ((int64_t)1 << 30)) {
-    op_set_error("gemm_tn: shape M=%lld N=%lld K=%lld not supported by the transpose-read kernel", (long long)M, (long long)N,
-                 (long long)K);
+    op_set_error("gemm_tn: shape M=%lld N=%lld K=%lld ldc=%lld not supported by the transpose-read kernel", (long long)M, (long long)N,
+                 (long long)K, (long long)ldc);
     return OP_ENOTSUP;
   }
   if (M == 0 || N == 0) return OP_OK;

@@ -470,8 +470,8 @@ def gemm_plan(M, N, K, epilogue=EPI_BIAS, has_bias=True, workspace_bytes=SPLITK_
     return out[0], out[1], bool(out[2]), out[3]
 
 
-def gemm_tn_supported(K, M, N, lda, ldb):
-    return (K % 64 == 0 and M % 8 == 0 and N % 8 == 0 and lda % 8 == 0 and ldb % 8 == 0 and M >= 8 and N >= 8
+def gemm_tn_supported(K, M, N, lda, ldb, ldc=0):
+    return (K % 64 == 0 and M % 8 == 0 and N % 8 == 0 and lda % 8 == 0 and ldb % 8 == 0 and ldc % 8 == 0 and M >= 8 and N >= 8
             and 31 * lda + M < (1 << 30) and 31 * ldb + N < (1 << 30))
 
 

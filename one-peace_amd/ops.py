@@ -270,7 +270,7 @@ def wgrad(dy, x, out=None, accumulate=False):
     K, M = dy.shape
     N = x.shape[1]
     K0 = wgrad_tn_rows(K)
-    if K0 >= 64 and hip.gemm_tn_supported(K0, M, N, dy.stride(0), x.stride(0)):
+    if K0 >= 64 and hip.gemm_tn_supported(K0, M, N, dy.stride(0), x.stride(0), out.stride(0) if out is not None else 0):
         out = hip.gemm_tn(dy[:K0], x[:K0], out, accumulate)
         if K0 != K:
             hip.gemm_tn(_tail_pad(dy, K0, 0), _tail_pad(x, K0, 1), out, True)

@@ -1,5 +1,10 @@
 """Op-level parity: every C-ABI kernel against the CPU oracle (fp32) on identical bf16-rounded inputs.
-Tolerances are the ones stated in tests/util.py."""
+Tolerances are the ones stated in tests/util.py.
+
+The GEMM tests here reach the launch routes with ONE input family, an fp32 reference and aggregate gates (relative Frobenius norm and
+largest error over the largest entry).  The per-element check of the same kernels against fp64 -- every route asserted by name, hard
+input families, outputs in guarded buffers -- is tests/test_gemm_fp64_gpu.py (reference, budget and cases: tests/gemm_ref.py, checked
+on the CPU by tests/test_gemm_ref_cpu.py)."""
 import math
 
 import pytest
