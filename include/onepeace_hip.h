@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* ---- library ------------------------------------------------------------------------------------------------ */
-int op_abi_version(void); /* 2: per-call `tune` words replaced the process-wide knob setters; 3: op_gemm_nt_grouped, op_ln_geglu_fwd, ldd / ldh of op_ln_geglu_bwd, `out` of op_attn_bwd; 4: op_gemm_tn_grouped; 5: op_probe_mfma_rate, op_rows_gather / op_rows_merge, 16-byte rule of op_gemm_tn_grouped's C; 6: the op_probe_* entry points left for libonepeace_probe.so (include/onepeace_probe.h), op_gemm_nt_grouped answers OP_ENOTSUP for the GeGLU epilogue, op_gemm_tn_grouped_plan takes the workgroup count and tune word; 7: W / ldw / rowdot of op_gemm_tn_grouped, g0 of op_resid_bwd, op_gamma_grad_finish, op_gemm_nt_batched, op_audio_conv1_ln_gelu_fwd / _bwd; 8: the layer-scale gradient without a division -- rscale of op_gemm_tn_grouped, op_transpose_scaled + the scale member of the op_transpose_batched descriptor, op_resid_bwd leaves gamma out of dbranch when g0 is asked for, op_gamma_grad_finish lost its gamma argument; rowdot is a [N / 128][M] matrix of partial sums written once each (no atomics); 9: row tables -- a residual branch that runs on the samples stochastic depth keeps reads and writes the FULL activation matrix through op_rows_map's table instead of through packed copies: x_rows of op_layernorm_fwd / op_layernorm_bwd, dout_rows of op_resid_bwd, resid_rows / resid_rows_total of op_gemm_nt and op_gemm_nt_grouped, op_rows_merge without `upd` copies the dropped samples' rows only; op_prof_reserve; 10: run-to-run identical gradients -- op_relpos_bias_bwd sums the table gradient in a fixed order from pair lists instead of scattering with atomics, op_relpos_bias_bwd_ids became op_relpos_bias_fold_ids, the separate dBias kernel of op_attn_bwd adds into one slab per batch chunk */
+int op_abi_version(void); /* 2: per-call `tune` words replaced the process-wide knob setters; 3: op_gemm_nt_grouped, op_ln_geglu_fwd, ldd / ldh of op_ln_geglu_bwd, `out` of op_attn_bwd; 4: op_gemm_tn_grouped; 5: op_probe_mfma_rate, op_rows_gather / op_rows_merge, 16-byte rule of op_gemm_tn_grouped's C; 6: the op_probe_* entry points left for libonepeace_probe.so (include/onepeace_probe.h), op_gemm_nt_grouped answers OP_ENOTSUP for the GeGLU epilogue, op_gemm_tn_grouped_plan takes the workgroup count and tune word; 7: W / ldw / rowdot of op_gemm_tn_grouped, g0 of op_resid_bwd, op_gamma_grad_finish, op_gemm_nt_batched, op_audio_conv1_ln_gelu_fwd / _bwd; 8: the layer-scale gradient without a division -- rscale of op_gemm_tn_grouped, op_transpose_scaled + the scale member of the op_transpose_batched descriptor, op_resid_bwd leaves gamma out of dbranch when g0 is asked for, op_gamma_grad_finish lost its gamma argument; rowdot is a [N / 128][M] matrix of partial sums written once each (no atomics); 9: row tables -- a residual branch that runs on the samples stochastic depth keeps reads and writes the FULL activation matrix through op_rows_map's table instead of through packed copies: x_rows of op_layernorm_fwd / op_layernorm_bwd, dout_rows of op_resid_bwd, resid_rows / resid_rows_total of op_gemm_nt and op_gemm_nt_grouped, op_rows_merge without `upd` copies the dropped samples' rows only; op_prof_reserve; 10: run-to-run identical gradients -- op_relpos_bias_bwd sums the table gradient in a fixed order from pair lists instead of scattering with atomics, op_relpos_bias_bwd_ids became op_relpos_bias_fold_ids, the separate dBias kernel of op_attn_bwd adds into one slab per batch chunk; (still 10, additive) op_live_ktiles + op_gemm_tn_grouped_lists: the weight gradients skip the K-tiles of samples stochastic depth dropped */
 const char* op_last_error(void);
 
 /* Live per-kernel-family timing with HIP events recorded on the launch stream (used by bench.py's `roofline`).
@@ -151,6 +151,26 @@ int op_gemm_tn_grouped(int64_t nprob, const void* const* A, const int64_t* lda, 
                        const int64_t* ldc, const int64_t* M, const int64_t* N, const int64_t* K, const int32_t* accumulate,
                        const void* const* W, const int64_t* ldw, float* const* rowdot, const void* const* rscale, void* counters,
                        int64_t tune, void* stream);
+/* op_gemm_tn_grouped with live K-tile lists.  ktiles / n_ktiles: nullable HOST arrays of nprob nullable DEVICE pointers; a problem with
+ * ktiles[i] != NULL (then n_ktiles[i] too) runs only the 64-row K-tiles ktiles[i][0 .. *n_ktiles[i]) -- ascending int32 tile indices
+ * < K_i / 64, written on the device before the launch (op_live_ktiles), never read by the host -- instead of all K_i / 64.  The rows of
+ * A_i in the tiles left out must be zero (a residual branch's gradient rows of the samples stochastic depth dropped: op_resid_bwd
+ * multiplied them by ps = 0): every fp32 accumulator starts at +0 and a +-0 product leaves it bit for bit what it was, so C_i and
+ * rowdot_i equal those of the full launch -- unless B_i holds inf / NaN in such a row (0 * inf = NaN is then skipped, not computed).
+ * An empty list leaves an accumulated C_i untouched and writes zeros otherwise; rowdot_i is written (zeros) either way.  A problem
+ * without a list runs as in op_gemm_tn_grouped, which is this entry point with both arrays NULL.  Additive: op_abi_version() stays 10. */
+int op_gemm_tn_grouped_lists(int64_t nprob, const void* const* A, const int64_t* lda, const void* const* B, const int64_t* ldb, void* const* C,
+                             const int64_t* ldc, const int64_t* M, const int64_t* N, const int64_t* K, const int32_t* accumulate,
+                             const void* const* W, const int64_t* ldw, float* const* rowdot, const void* const* rscale,
+                             const int32_t* const* ktiles, const int32_t* const* n_ktiles, void* counters, int64_t tune, void* stream);
+/* Live K-tile lists of up to 8 weight-gradient problems over ONE row matrix in one tiny launch, no host synchronisation.  Segments
+ * (HOST arrays, nseg <= 4): rows [row0_i, row0_i + S_i * B_i) are B_i samples of S_i rows with DEVICE multipliers ps_i (fp32 [B_i];
+ * NULL entry: all kept); rows of no segment belong to no sample.  Problems (HOST arrays, nprob <= 8): rows [prob_row0_p, prob_row0_p +
+ * prob_rows_p), prob_rows_p % 64 == 0.  ktiles[p] (DEVICE int32 [prob_rows_p / 64]) receives, ascending and relative to prob_row0_p,
+ * the indices of the 64-row tiles that hold a row of a sample with ps != 0; n_ktiles[p] (DEVICE int32) their number.
+ * Additive: op_abi_version() stays 10. */
+int op_live_ktiles(int64_t nseg, const float* const* ps, const int64_t* row0, const int64_t* S, const int64_t* B, int64_t nprob,
+                   const int64_t* prob_row0, const int64_t* prob_rows, int32_t* const* ktiles, int32_t* const* n_ktiles, void* stream);
 /* `tune` (op_gemm_nt, op_gemm_tn, op_gemm_plan): per-call tuning word, 0 = what production uses.  The library keeps NO tuning
  * state, so every entry point is a pure function of its arguments; tests and tools select a kernel flavour with the call:
  * bits 0-1 tile (0 auto: a cost model picks 128x128 or 256x256 tiles, K-splits and the tail-rows split; 1 force 128x128;

@@ -740,6 +740,56 @@ __global__ __launch_bounds__(256) void rows_map_kernel(int* __restrict__ map, co
   map[rc] = (int)from;
 }
 
+// Live K-tile lists for the weight gradients of a residual branch whose dropped samples have an all-zero gradient (op_resid_bwd wrote
+// ps * dout with ps = 0): problem p covers the rows [row0, row0 + 64 * ntiles) of the row matrix; its list names, in ascending order,
+// the 64-row tiles that hold at least one row of a sample with ps != 0.  One workgroup per problem; the flags of 256 tiles at a time
+// are compacted in order (ballot + the counts of the waves before).
+constexpr int LK_MAX_SEG = 4, LK_MAX_PROB = 8;
+struct LiveTilesArgs {
+  int nseg;
+  struct { const float* ps; int64_t row0; int S, B; } seg[LK_MAX_SEG];  // rows [row0, row0 + S * B); row r belongs to sample (r - row0) / S
+  struct { int64_t row0; int ntiles; int* list; int* count; } prob[LK_MAX_PROB];
+};
+
+__global__ __launch_bounds__(256) void live_ktiles_kernel(const LiveTilesArgs a) {
+  __shared__ int wave_n[4];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int64_t prow0 = a.prob[blockIdx.x].row0;
+  const int ntiles = a.prob[blockIdx.x].ntiles;
+  int* __restrict__ list = a.prob[blockIdx.x].list;
+  int base = 0;  // (uniform) live tiles before this chunk
+  for (int c = 0; c < ntiles; c += 256) {
+    const int t = c + tid;
+    bool live = false;
+    if (t < ntiles) {
+      const int64_t r0 = prow0 + (int64_t)t * 64, r1 = r0 + 64;
+#pragma unroll
+      for (int i = 0; i < LK_MAX_SEG; ++i) {
+        if (i >= a.nseg) continue;
+        const int64_t lo = r0 > a.seg[i].row0 ? r0 : a.seg[i].row0;
+        const int64_t end = a.seg[i].row0 + (int64_t)a.seg[i].S * a.seg[i].B;
+        const int64_t hi = r1 < end ? r1 : end;
+        if (lo >= hi) continue;
+        if (a.seg[i].ps == nullptr) { live = true; continue; }
+        const int s0 = (int)((lo - a.seg[i].row0) / a.seg[i].S), s1 = (int)((hi - 1 - a.seg[i].row0) / a.seg[i].S);
+        for (int sm = s0; sm <= s1; ++sm) live = live || a.seg[i].ps[sm] != 0.f;
+      }
+    }
+    const unsigned long long m = __ballot(live);
+    if (lane == 0) wave_n[wid] = __popcll(m);
+    __syncthreads();
+    int before = base;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      if (w < wid) before += wave_n[w];
+      base += wave_n[w];
+    }
+    if (live) list[before + __popcll(m & ((1ull << lane) - 1ull))] = t;
+    __syncthreads();
+  }
+  if (tid == 0) *a.prob[blockIdx.x].count = base;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1099,6 +1149,34 @@ int op_rows_map(int* map, const int* list, int64_t nseg, const int64_t* src_row0
   OP_CHECK_ARG(rows_segs(d, nseg, src_row0, dst_row0, S, n_kept, dst_rows, n_samples, list_off), "rows_map: bad segment table");
   if (dst_total == 0) return OP_OK;
   hipLaunchKernelGGL(rows_map_kernel, dim3((int)((dst_total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, map, list, d, dst_total);
+  OP_LAUNCH_CHECK();
+  return OP_OK;
+}
+
+// Live K-tile lists of up to 8 weight-gradient problems over one row matrix, ONE launch, no host synchronisation (see
+// live_ktiles_kernel; consumer: op_gemm_tn_grouped_lists).  Segments (HOST arrays of nseg <= 4 entries): rows [row0_i, row0_i + S_i * B_i)
+// belong to B_i samples of S_i rows with the DEVICE multipliers ps_i (fp32 [B_i]; a null entry: every sample kept); rows of no segment
+// belong to no sample.  Problems (HOST arrays of nprob entries): rows [prob_row0_p, prob_row0_p + prob_rows_p), prob_rows_p % 64 == 0;
+// ktiles[p]: DEVICE int32 [prob_rows_p / 64] receives the ascending indices (relative to prob_row0_p) of the 64-row tiles with a row of
+// a sample whose ps != 0, n_ktiles[p]: DEVICE int32 their number.
+int op_live_ktiles(int64_t nseg, const float* const* ps, const int64_t* row0, const int64_t* S, const int64_t* B, int64_t nprob,
+                   const int64_t* prob_row0, const int64_t* prob_rows, int32_t* const* ktiles, int32_t* const* n_ktiles, void* stream) {
+  OP_CHECK_ARG(nseg >= 1 && nseg <= LK_MAX_SEG && nprob >= 1 && nprob <= LK_MAX_PROB, "live_ktiles: %lld segments (1 ... %d), %lld problems (1 ... %d)",
+               (long long)nseg, LK_MAX_SEG, (long long)nprob, LK_MAX_PROB);
+  OP_CHECK_ARG(ps && row0 && S && B && prob_row0 && prob_rows && ktiles && n_ktiles, "live_ktiles: null pointer");
+  LiveTilesArgs a;
+  memset(&a, 0, sizeof(a));
+  a.nseg = (int)nseg;
+  for (int i = 0; i < (int)nseg; ++i) {
+    OP_CHECK_ARG(row0[i] >= 0 && S[i] >= 1 && B[i] >= 1 && S[i] < ((int64_t)1 << 31) && B[i] < ((int64_t)1 << 31), "live_ktiles: bad segment %d", i);
+    a.seg[i].ps = ps[i]; a.seg[i].row0 = row0[i]; a.seg[i].S = (int)S[i]; a.seg[i].B = (int)B[i];
+  }
+  for (int p = 0; p < (int)nprob; ++p) {
+    OP_CHECK_ARG(prob_row0[p] >= 0 && prob_rows[p] >= 64 && prob_rows[p] % 64 == 0 && prob_rows[p] / 64 < ((int64_t)1 << 31) && ktiles[p] && n_ktiles[p],
+                 "live_ktiles: bad problem %d", p);
+    a.prob[p].row0 = prob_row0[p]; a.prob[p].ntiles = (int)(prob_rows[p] / 64); a.prob[p].list = ktiles[p]; a.prob[p].count = n_ktiles[p];
+  }
+  hipLaunchKernelGGL(live_ktiles_kernel, dim3((int)nprob), dim3(256), 0, (hipStream_t)stream, a);
   OP_LAUNCH_CHECK();
   return OP_OK;
 }

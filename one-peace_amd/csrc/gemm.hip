@@ -1645,6 +1645,9 @@ struct TnProb {
   // (round 6) rscale != nullptr (only with rowdot): C[m][:] += rscale[m] * product[m][:], while rowdot sums W * the UNSCALED product -- with A the
   // un-gamma-scaled branch gradient, rscale = gamma and W the last Linear's weight, rowdot IS the layer-scale gradient (no division)
   const bf16_t* W; int64_t ldw; float* rowdot; const bf16_t* rscale;
+  // optional (op_gemm_tn_grouped_lists): ktiles[0 .. *n_ktiles) = the 64-row K-tiles to run, ascending (device memory, written by
+  // op_live_ktiles before the launch) -- the others hold only zero rows of A (samples stochastic depth dropped) and are not fetched
+  const int* ktiles; const int* n_ktiles;
 };
 // A queue is a list of RUNS: `n` consecutive slots of one problem's slot order (below), from slot0 on.
 struct TnRun { int prob_n; int slot0; };  // prob_n = problem << 24 | n
@@ -1884,7 +1887,13 @@ __global__ __launch_bounds__(256) void gemm256w_tn_grouped_kernel(const TnGroupA
       const int M = q.M, N = q.N;
       const int64_t lda = q.lda, ldb = q.ldb;
       const int m0 = pid_m * BM2, n0 = pid_n * 256;
-      const int nk = q.K / BK2;
+      // K-tile list (wave-uniform; read through the constant address space: scalar loads, nothing in this launch writes the list).
+      // An entry is a 64-row tile = TWO steps of BK2 rows: the even step of a pair takes its rows from the list, the odd one follows it.
+      typedef const __attribute__((address_space(4))) int* TnList;
+      const bool listed = q.ktiles != nullptr;
+      const TnList kl = (TnList)(uintptr_t)(listed ? (const void*)q.ktiles : (const void*)q.A);
+      int nk = q.K / BK2;
+      if (listed) nk = 2 * max(0, min(*(TnList)(uintptr_t)q.n_ktiles, nk >> 1));
       const char* baseA = (const char*)q.A;
       const char* baseB = (const char*)q.B;
       unsigned offA[4], offB[4];
@@ -1937,10 +1946,27 @@ __global__ __launch_bounds__(256) void gemm256w_tn_grouped_kernel(const TnGroupA
         const bf16x8 wv = join16(f.w[ff][0], f.w[ff][1]), xv = join16(f.x[mi][0], f.x[mi][1]);
         asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[ff >> 2][ff & 3][mi]) : "v"(wv), "v"(xv));
       };
-      auto step_steady = [&](int kt, const Frags& cur, Frags& nxt) {
+      // A listed pair of steps: the rows of the stage its even step fetches (step kt + STAGES2 = entry kt / 2 + 2) come from tile_next,
+      // read one pair ago -- the operand pointers stand one tile behind tile_prev by then and jump over the dropped tiles between the
+      // two; the entry after it is requested HERE, behind the wait on lgkmcnt the step starts with anyway, and is first used behind
+      // the same wait of the next pair: the scalar load never stands between the fragment reads and their MFMAs.
+      int tile_prev = 0, tile_next = 0;
+      auto step_steady = [&](int kt, const Frags& cur, Frags& nxt, bool even) {
         WAIT_LGKM(0);
         WAIT_VM(16);
         __builtin_amdgcn_s_barrier();
+        if (even) {
+          if (listed) {  // (wave-uniform)
+            const int gap = tile_next - tile_prev - 1;
+            baseA += (int64_t)gap * (2 * stepA);
+            baseB += (int64_t)gap * (2 * stepB);
+            tile_prev = tile_next;
+          }
+          // Outside the branch: a value defined under it would reach the next pair through a copy, and the copy would wait for the load
+          // right here.  (A problem without a list reads a word of its A operand and never looks at it.)
+          tile_next = kl[listed ? min((kt >> 1) + 3, (nk >> 1) - 1) : 0];
+          __builtin_amdgcn_sched_barrier(0);
+        }
         const char* st = smem + ((kt + 1) & (STAGES2 - 1)) * STAGE2_BYTES;
         char* la = smem + (kt & (STAGES2 - 1)) * STAGE2_BYTES;
 #pragma unroll
@@ -1967,9 +1993,25 @@ __global__ __launch_bounds__(256) void gemm256w_tn_grouped_kernel(const TnGroupA
         for (int j = 0; j < 64; ++j) mfma1(cur, j);
       };
 
+      if (listed && nk > 0) {  // (STAGES2 = 4: the first two entries fill the stages)
+        const int t0 = kl[0];
+        tile_prev = kl[min(1, (nk >> 1) - 1)];
+        tile_next = kl[min(2, (nk >> 1) - 1)];
+        baseA += (int64_t)t0 * (2 * stepA);
+        baseB += (int64_t)t0 * (2 * stepB);
+        issue(0);
+        issue(1);
+        if (nk > 2) {
+          baseA += (int64_t)(tile_prev - t0 - 1) * (2 * stepA);
+          baseB += (int64_t)(tile_prev - t0 - 1) * (2 * stepB);
+          issue(2);
+          issue(3);
+        }
+      } else {
 #pragma unroll
-      for (int s0 = 0; s0 < STAGES2; ++s0)
-        if (s0 < nk) issue(s0);
+        for (int s0 = 0; s0 < STAGES2; ++s0)
+          if (s0 < nk) issue(s0);
+      }
       Frags fA, fB;
       wait_landed(min(nk - 1, STAGES2 - 1));
       __builtin_amdgcn_s_barrier();
@@ -1977,8 +2019,8 @@ __global__ __launch_bounds__(256) void gemm256w_tn_grouped_kernel(const TnGroupA
       for (int r = 0; r < 32; ++r) rd(smem, fA, r);
       int kt = 0;
       for (; kt + STAGES2 + 1 < nk; kt += 2) {
-        step_steady(kt, fA, fB);
-        step_steady(kt + 1, fB, fA);
+        step_steady(kt, fA, fB, true);
+        step_steady(kt + 1, fB, fA, false);
       }
       for (; kt < nk; kt += 2) {
         step_tail(kt, fA, fB);
@@ -1999,7 +2041,9 @@ __global__ __launch_bounds__(256) void gemm256w_tn_grouped_kernel(const TnGroupA
       // became free found the queues empty and left: finish times spread over 700 us of a 4.5 ms launch.)
       auto draw_next = [&]() { if (tid == 0) draw(); };
       __syncthreads();  // every wave is out of the main loop: the operand stages are free for the epilogue
-      {
+      if (nk == 0 && q.accumulate && q.rowdot == nullptr) {  // (uniform) an empty list adds nothing: the gradient tile is left untouched
+        draw_next();
+      } else {
         char* wlds = smem + wid * 32768;
         const int mr = m0 + wm * 128, nb = n0 + wn * 128;
         if (m0 + 256 <= M && n0 + 256 <= N) {  // (uniform) tile inside the matrix
@@ -2806,10 +2850,13 @@ int64_t op_gemm_tn_grouped_plan(int64_t nprob, const int64_t* M, const int64_t* 
 // launched) when a problem does not qualify -- the caller then uses op_gemm_tn per problem.  Problems may come in any order.
 // The gradient is read-modify-written in 16-byte pieces: ldc_i % 8 == 0 and C_i 16-byte aligned as well.
 // tune: bits 0-9 = forced number of workgroups (0: one per CU, at most one per tile); bit 10 = round 4's solo workgroups (see the kernel).
-int op_gemm_tn_grouped(int64_t nprob, const void* const* A, const int64_t* lda, const void* const* B, const int64_t* ldb, void* const* C,
-                       const int64_t* ldc, const int64_t* M, const int64_t* N, const int64_t* K, const int32_t* accumulate,
-                       const void* const* W, const int64_t* ldw, float* const* rowdot, const void* const* rscale, void* counters, int64_t tune,
-                       void* stream) {
+// ktiles / n_ktiles (op_gemm_tn_grouped_lists): nullable HOST arrays of nullable DEVICE pointers -- problem i runs only the 64-row
+// K-tiles ktiles[i][0 .. *n_ktiles[i]) (ascending; op_live_ktiles).  The schedule still deals by the nominal K: how many tiles are
+// live is known on the device only, and stealing evens out what the lists take away.
+int op_gemm_tn_grouped_lists(int64_t nprob, const void* const* A, const int64_t* lda, const void* const* B, const int64_t* ldb, void* const* C,
+                             const int64_t* ldc, const int64_t* M, const int64_t* N, const int64_t* K, const int32_t* accumulate,
+                             const void* const* W, const int64_t* ldw, float* const* rowdot, const void* const* rscale,
+                             const int32_t* const* ktiles, const int32_t* const* n_ktiles, void* counters, int64_t tune, void* stream) {
   OP_CHECK_ARG(nprob >= 1 && nprob <= TN_MAX_PROB, "gemm_tn_grouped: %lld problems (1 ... %d)", (long long)nprob, TN_MAX_PROB);
   OP_CHECK_ARG(A && lda && B && ldb && C && ldc && M && N && K && accumulate && counters, "gemm_tn_grouped: null pointer");
   int order[TN_MAX_PROB];
@@ -2848,6 +2895,10 @@ int op_gemm_tn_grouped(int64_t nprob, const void* const* A, const int64_t* lda, 
     } else {
       OP_CHECK_ARG(rscale == nullptr || rscale[s] == nullptr, "gemm_tn_grouped: problem %d: rscale rides on the rowdot epilogue (rowdot is null)", s);
     }
+    if (ktiles != nullptr && ktiles[s] != nullptr) {
+      OP_CHECK_ARG(n_ktiles != nullptr && n_ktiles[s] != nullptr, "gemm_tn_grouped: problem %d has a K-tile list without its count", s);
+      q.ktiles = ktiles[s]; q.n_ktiles = n_ktiles[s];
+    }
     tiles += (int64_t)q.tiles_m * q.tiles_n;
     work += 2.0 * (double)M[s] * (double)N[s] * (double)K[s];
   }
@@ -2862,6 +2913,14 @@ int op_gemm_tn_grouped(int64_t nprob, const void* const* A, const int64_t* lda, 
   op_prof_end(slot, stream);
   OP_LAUNCH_CHECK();
   return OP_OK;
+}
+
+int op_gemm_tn_grouped(int64_t nprob, const void* const* A, const int64_t* lda, const void* const* B, const int64_t* ldb, void* const* C,
+                       const int64_t* ldc, const int64_t* M, const int64_t* N, const int64_t* K, const int32_t* accumulate,
+                       const void* const* W, const int64_t* ldw, float* const* rowdot, const void* const* rscale, void* counters, int64_t tune,
+                       void* stream) {
+  return op_gemm_tn_grouped_lists(nprob, A, lda, B, ldb, C, ldc, M, N, K, accumulate, W, ldw, rowdot, rscale, nullptr, nullptr, counters, tune,
+                                  stream);
 }
 
 }  // extern "C"

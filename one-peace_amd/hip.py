@@ -42,6 +42,8 @@ SIGNATURES = {
     "op_gemm_tn_grouped_counter_bytes": (I64, []),
     "op_gemm_tn_grouped_plan": (I64, [I64, P, P, P, I64, I64, P, I64]),
     "op_gemm_tn_grouped": (c_int, [I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P]),
+    "op_gemm_tn_grouped_lists": (c_int, [I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P]),
+    "op_live_ktiles": (c_int, [I64, P, P, P, P, I64, P, P, P, P, P]),
     "op_gemm_nt_batched": (c_int, [P, I64, I64, P, I64, I64, P, I64, P, I64, I64, I64, I64, I64, I64, P]),
     "op_audio_conv1_ln_gelu_fwd": (c_int, [P, I64, P, P, P, P, P, P, P, I64, I64, c_float, P]),
     "op_audio_conv1_ln_gelu_bwd_workspace_bytes": (I64, [I64]),
@@ -545,12 +547,33 @@ _tn_counters = {}
 TN_GROUP_MAX = 16
 
 
-def gemm_tn_grouped(problems, tune=0):
+def live_ktiles(segs, probs, device):
+    """Live K-tile lists (op_live_ktiles) for weight-gradient problems over one row matrix whose rows of dropped samples are zero.
+    segs: [(ps fp32 [B] | None, row0, S, B)]; probs: [(row0, rows)], rows % 64 == 0.  Returns per problem (list int32 [rows / 64], count
+    int32 [1]): views of ONE buffer, filled by one launch, never read by the host."""
+    ns, n = len(segs), len(probs)
+    sizes = [rows // 64 for _, rows in probs]
+    buf = torch.empty(sum(sizes) + n, dtype=torch.int32, device=device)
+    lists, off = [], n
+    for p, k in enumerate(sizes):
+        lists.append((buf[off:off + k], buf[p:p + 1]))
+        off += k
+    i64 = lambda k, vals: (c_int64 * k)(*[int(v) for v in vals])  # noqa: E731
+    for ps, _, _, B in segs:
+        assert ps is None or (ps.dtype == torch.float32 and ps.is_contiguous() and ps.numel() >= B and ps.device == buf.device)
+    _check(lib().op_live_ktiles(ns, _ptr_array([q[0] for q in segs], ns), i64(ns, [q[1] for q in segs]), i64(ns, [q[2] for q in segs]),
+                                i64(ns, [q[3] for q in segs]), n, i64(n, [q[0] for q in probs]), i64(n, [q[1] for q in probs]),
+                                _ptr_array([q[0] for q in lists], n), _ptr_array([q[1] for q in lists], n), stream()), "op_live_ktiles")
+    return lists
+
+
+def gemm_tn_grouped(problems, tune=0, ktiles=None):
     """ONE persistent launch for up to 16 weight-gradient GEMMs, no split-K (csrc/gemm.hip: gemm256w_tn_grouped_kernel).
     problems: [(A_km [K, M], B_kn [K, N], out [M, N] bf16, accumulate[, (W [M, N] bf16, rowdot fp32 [N / 128, M][, rscale bf16 [M]])])].
     Returns False (nothing launched) when a problem does not qualify for the transpose-read kernel -- the caller then runs gemm_tn per
     problem.  (W, rowdot): rowdot[s][m] = sum over the 128 columns n of slot s of W[m][n] * (this launch's fp32 product)[m][n] (written,
-    every entry once); rscale: out[m] += rscale[m] * product[m] while rowdot sums the unscaled product -- see gamma_grad_finish."""
+    every entry once); rscale: out[m] += rscale[m] * product[m] while rowdot sums the unscaled product -- see gamma_grad_finish.
+    ktiles: per problem None or live_ktiles' (list, count): only those 64-row K-tiles run (the rows of A in the others are zero)."""
     n = len(problems)
     dev = problems[0][0].device
     key = (dev, torch.cuda.current_stream(dev).cuda_stream)
@@ -566,12 +589,18 @@ def gemm_tn_grouped(problems, tune=0):
     for sc, r, a, b in zip(Ss, Rs, As, Bs):
         assert sc is None or (sc.dtype == torch.bfloat16 and sc.is_contiguous() and sc.numel() == a.shape[1])
         assert r is None or (r.dtype == torch.float32 and r.is_contiguous() and r.shape == (b.shape[1] // 128, a.shape[1])), "rowdot: fp32 [N / 128, M]"
-    rc = lib().op_gemm_tn_grouped(n, _ptr_array(As, n), arr([a.stride(0) for a in As]), _ptr_array(Bs, n), arr([b.stride(0) for b in Bs]),
-                                  _ptr_array(Cs, n), arr([c.stride(0) for c in Cs]), arr([a.shape[1] for a in As]),
-                                  arr([b.shape[1] for b in Bs]), arr([a.shape[0] for a in As]), acc,
-                                  _ptr_array(Ws, n) if has_side else None, arr([w.stride(0) if w is not None else 0 for w in Ws]) if has_side else None,
-                                  _ptr_array(Rs, n) if has_side else None, _ptr_array(Ss, n) if any(x is not None for x in Ss) else None,
-                                  ptr(ctr), int(tune), stream())
+    head = (n, _ptr_array(As, n), arr([a.stride(0) for a in As]), _ptr_array(Bs, n), arr([b.stride(0) for b in Bs]),
+            _ptr_array(Cs, n), arr([c.stride(0) for c in Cs]), arr([a.shape[1] for a in As]),
+            arr([b.shape[1] for b in Bs]), arr([a.shape[0] for a in As]), acc,
+            _ptr_array(Ws, n) if has_side else None, arr([w.stride(0) if w is not None else 0 for w in Ws]) if has_side else None,
+            _ptr_array(Rs, n) if has_side else None, _ptr_array(Ss, n) if any(x is not None for x in Ss) else None)
+    if ktiles is not None and any(k is not None for k in ktiles):
+        for k, a in zip(ktiles, As):
+            assert k is None or (k[0].dtype == torch.int32 and k[1].dtype == torch.int32 and k[0].numel() >= a.shape[0] // 64)
+        rc = lib().op_gemm_tn_grouped_lists(*head, _ptr_array([k[0] if k is not None else None for k in ktiles], n),
+                                            _ptr_array([k[1] if k is not None else None for k in ktiles], n), ptr(ctr), int(tune), stream())
+    else:
+        rc = lib().op_gemm_tn_grouped(*head, ptr(ctr), int(tune), stream())
     if rc == -95:
         return False
     _check(rc, "op_gemm_tn_grouped")

@@ -284,6 +284,25 @@ def wgrad(dy, x, out=None, accumulate=False):
 # deferred weight gradients: all dW GEMMs of an encoder layer as ONE grouped launch (csrc/gemm.hip: gemm256w_tn_grouped_kernel)
 # --------------------------------------------------------------------------------------------------------------
 GROUPED_WGRAD = os.environ.get("ONEPEACE_GROUPED_WGRAD", "1") != "0"
+# The multiplier form of stochastic depth (the default; NOT skip_dropped_branches) sends every sample through every branch and
+# multiplies a dropped sample's branch output by ps = 0; in backward that zero is the INPUT: op_resid_bwd writes ps * dout, so the rows
+# of a dropped sample are zero in every gradient matrix of the branch.  "1": the weight gradients (whose K dimension is the token rows)
+# run only the 64-row K-tiles that hold a row of a kept sample (hip.live_ktiles, one tiny launch per branch, the masks never leave
+# the device) -- the same bits, since a +-0 product leaves an fp32 accumulator what it was; the one exception is a non-finite
+# activation in a dropped sample's row (0 * inf = NaN is skipped, as with skip_dropped_branches).  "0": every tile runs (A/B, tests).
+SKIP_ZERO_BACKWARD = os.environ.get("ONEPEACE_SKIP_ZERO_BACKWARD", "1") != "0"
+
+
+def _live_ktiles(segs, probs, device):
+    """Per problem of `probs` ([(row0, rows)]) its live K-tile list for the grouped weight-gradient launch, or None when the lists do
+    not apply: switched off, no multipliers, or a row range the 64-row tiles / the samples do not tile exactly (padded segments)."""
+    if not (SKIP_ZERO_BACKWARD and GROUPED_WGRAD) or all(q[0] is None for q in segs):
+        return [None] * len(probs)
+    if any(rows % 64 != 0 or rows < 64 for _, rows in probs) or len(segs) > 4 or len(probs) > 8:
+        return [None] * len(probs)
+    if any(ps is not None and (ps.dtype != torch.float32 or not ps.is_contiguous() or ps.numel() < B) for ps, _, _, B in segs):
+        return [None] * len(probs)
+    return hip.live_ktiles(segs, probs, device)
 
 
 class _WgradQueue:
@@ -294,12 +313,14 @@ class _WgradQueue:
 
     def __init__(self):
         self.items, self.done, self.after, self.armed, self.epoch = [], [], [], False, 0
+        self.lists = []  # per item: hip.live_ktiles' (list, count) or None
 
     def reset(self):
         """Forget everything a backward pass that raised left behind (the engine does not run queue_callback callbacks then):
         stale operands must not be accumulated into the freshly zeroed gradients of the next step, and the end-of-backward
         safety net has to be registered again.  Called by distributed.FlatParameters.zero_grad / BucketedGradReducer.reset."""
         self.items, self.done, self.after, self.armed = [], [], [], False
+        self.lists = []
         self.epoch += 1
 
     @staticmethod
@@ -308,10 +329,11 @@ class _WgradQueue:
         lo = out.data_ptr()
         return lo, lo + ((out.shape[0] - 1) * out.stride(0) + out.shape[1]) * out.element_size()
 
-    def add(self, dy, x, out, params, side=None, after=None):
+    def add(self, dy, x, out, params, side=None, after=None, ktiles=None):
         """side: (W, rowdot [N / 128, M], gamma) -- `dy` carries NO layer scale: the launch adds gamma[m] * product[m] to out[m] and writes the
         partial sums of W[m][n] * product[m][n] over 128-column slots to rowdot (hip.gemm_tn_grouped: rscale);
-        after: called once the launch that holds this problem is enqueued (before the parameters are reported)."""
+        after: called once the launch that holds this problem is enqueued (before the parameters are reported);
+        ktiles: (list, count) of _live_ktiles -- the rows of dy outside those 64-row tiles are zero."""
         lo, hi = self._span(out)
         for it in self.items:  # the grouped launch read-modify-writes C tiles without ordering between problems: two
             l2, h2 = self._span(it[2])  # contributions to one (overlapping) view go out as two launches, stream-ordered
@@ -319,6 +341,7 @@ class _WgradQueue:
                 self.flush()
                 break
         self.items.append((dy, x, out, True, side))
+        self.lists.append(ktiles)
         self.done.extend(params)
         if after is not None:
             self.after.append(after)
@@ -336,10 +359,11 @@ class _WgradQueue:
         self.flush()
 
     def flush(self):
-        items, done, after = self.items, self.done, self.after
-        self.items, self.done, self.after = [], [], []
+        items, done, after, lists = self.items, self.done, self.after, self.lists
+        self.items, self.done, self.after, self.lists = [], [], [], []
         if items:
-            if len(items) == 1 or not hip.gemm_tn_grouped(items):  # a lone problem keeps the split-K launch of op_gemm_tn
+            kw = {"ktiles": lists} if any(k is not None for k in lists) else {}
+            if len(items) == 1 or not hip.gemm_tn_grouped(items, **kw):  # a lone problem keeps the split-K launch of op_gemm_tn
                 for dy, x, out, _, side in items:
                     if side is None:
                         hip.gemm_tn(dy, x, out, True)
@@ -365,13 +389,13 @@ def _wgrad_queueable(K, M, N, ldy, ldx, grad_view):
             and hip.gemm_tn_supported(K, M, N, ldy, ldx))
 
 
-def wgrad_into(dy, x, grad_view, params, side=None, after=None):
+def wgrad_into(dy, x, grad_view, params, side=None, after=None, ktiles=None):
     """grad_view (+)= dy^T x for the flat-buffer gradient views of `params` (one view spanning all of them).  Deferred into the
     layer's grouped launch when the shape allows, else launched now; either way every parameter's completion is signalled.
     side / after: see _WgradQueue.add (the caller has checked dgamma_from_wgrad_ok: the problem IS queueable)."""
     K, M = dy.shape
     if _wgrad_queueable(K, M, x.shape[1], dy.stride(0), x.stride(0), grad_view):
-        _wgrad_queue.add(dy, x, grad_view, params, side, after)
+        _wgrad_queue.add(dy, x, grad_view, params, side, after, ktiles)
         return
     assert side is None and after is None, "wgrad_into: a side product was promised for a problem the grouped launch does not take"
     wgrad(dy, x, out=grad_view, accumulate=True)
@@ -1000,10 +1024,10 @@ def _span(direct, order):
 def _weight_grad_fn(ctx, G):
     direct = dict(ctx.direct)
 
-    def weight_grad(name, dyv, xv, side=None, after=None):
+    def weight_grad(name, dyv, xv, side=None, after=None, ktiles=None):
         target = direct.get(name)
         if target is not None:
-            wgrad_into(dyv, xv, target.grad, (target,), side, after)
+            wgrad_into(dyv, xv, target.grad, (target,), side, after, ktiles)
         else:
             assert side is None and after is None
             G[name] = wgrad(dyv, xv)
@@ -1121,17 +1145,22 @@ class AttnBranchFn(torch.autograd.Function):
             dx_mid = hip.rows_gather(dx_full, kept)
         G = {}
         weight_grad, direct = _weight_grad_fn(ctx, G)
+        # out-proj and q|k|v weight gradients: both run over ALL rows, one list serves both (rows of dropped samples are zero in dy1, and
+        # so in everything the branch derives from it)
+        kt1 = None
+        if rowscale is not None and kept is None and N % rps == 0 and not any(sg.pad for sg in segs) and sum(sg.rows for sg in segs) == N:
+            kt1 = _live_ktiles([(rowscale, 0, rps, N // rps)], [(0, N)], dx_mid.device)[0]
         if ctx.dg_fused:  # dy1 = rowscale * dx_mid, WITHOUT gamma_1 (weight gradient: rscale; input gradient: scaled weight copy)
             g0 = torch.empty(H, dtype=torch.float32, device=dx_mid.device)
             dy1 = _resid_backward(dx_mid, None, P["g1"], rowscale, rps, "g1", "bo", direct, G, needs, g0=g0, rows=xmap)
             rowdot, (rd_wo,) = _rowdot_slots(dx_mid.device, [P["wo"]])
             weight_grad("wo", dy1, A["aln"], side=(P["wo"], rd_wo, P["g1"]),
-                        after=_gamma_finish_hook(rowdot, direct["g1"], [(P["bo"], g0)] if P["bo"] is not None else [], True))
+                        after=_gamma_finish_hook(rowdot, direct["g1"], [(P["bo"], g0)] if P["bo"] is not None else [], True), ktiles=kt1)
             wo_t = _transposed(P["wo"], scale=P["g1"])
         else:
             dy1 = _resid_backward(dx_mid, A["y1"], P["g1"], rowscale, rps, "g1", "bo", direct, G, needs, rows=xmap)
             if needs["wo"]:
-                weight_grad("wo", dy1, A["aln"])
+                weight_grad("wo", dy1, A["aln"], ktiles=kt1)
             wo_t = None
         upstream = ("ln1_w", "ln1_b", "wq", "bq", "wk", "wv", "bv", "aln_w", "aln_b")
         dx = None
@@ -1179,11 +1208,11 @@ class AttnBranchFn(torch.autograd.Function):
                         i = slot["wq" if n == "bq" else "wv"]
                         G[n] = sums[i * H:(i + 1) * H]
             if order:  # one problem: dW[3H, H] straight into the three adjacent flat gradient views
-                wgrad_into(dqkv, A["xln1"], _span(direct, order), [direct[n] for n in order])
+                wgrad_into(dqkv, A["xln1"], _span(direct, order), [direct[n] for n in order], ktiles=kt1)
             elif any(n in direct for n in qkv_names) or not all(needs[n] for n in qkv_names):
                 for n in qkv_names:
                     if needs[n]:
-                        weight_grad(n, dqkv[:, slot[n] * H:(slot[n] + 1) * H], A["xln1"])
+                        weight_grad(n, dqkv[:, slot[n] * H:(slot[n] + 1) * H], A["xln1"], ktiles=kt1)
             else:
                 dW = wgrad(dqkv, A["xln1"])  # [3H, H]
                 G["wq"], G["wk"], G["wv"] = dW[:H], dW[H:2 * H], dW[2 * H:]
@@ -1409,6 +1438,10 @@ class FfnBranchMultiFn(torch.autograd.Function):
         fused = ctx.dg_fused  # gamma_2's gradient from the three down-projection weight gradients (no y2: dgamma_from_wgrad_ok)
         fp8b = FP8_FFN and FP8_FFN_DGRAD and H % 128 == 0 and Fd % 128 == 0
         (rowdot, rd_views), pairs = (_rowdot_slots(dev, [P["w2@%d" % i] for i in range(nseg)]), []) if fused else ((None, None), None)
+        # per segment ONE list for its down-projection and wi_0 | wi_1 weight gradients (the segment's own rows), all in one launch
+        kts = [None] * nseg
+        if kept is None and not any(sg.pad for sg in segs):
+            kts = _live_ktiles([(pss[i], sg.row0, sg.S, sg.B) for i, sg in enumerate(segs)], [(sg.row0, sg.rows) for sg in segs], dev)
         for i, sg in enumerate(segs):
             r = slice(sg.row0, sg.end)
             k = lambda n: "%s@%d" % (n, i)  # noqa: E731
@@ -1421,9 +1454,9 @@ class FfnBranchMultiFn(torch.autograd.Function):
                                   "g2", k("b2"), direct, G, needs, g0=g0, rows=xmap[r] if mapped else None, fold=fold)
             if fused:  # (the hook rides on the last segment's problem: by then every (bias, g0) pair is listed)
                 weight_grad(k("w2"), dy2, A["gln"][r], side=(P[k("w2")], rd_views[i], P["g2"]),
-                            after=_gamma_finish_hook(rowdot, direct["g2"], pairs, True) if i == nseg - 1 else None)
+                            after=_gamma_finish_hook(rowdot, direct["g2"], pairs, True) if i == nseg - 1 else None, ktiles=kts[i])
             elif needs[k("w2")]:
-                weight_grad(k("w2"), dy2, A["gln"][r])
+                weight_grad(k("w2"), dy2, A["gln"][r], ktiles=kts[i])
             if not upstream:
                 colsets.append(None)
                 continue
@@ -1449,11 +1482,11 @@ class FfnBranchMultiFn(torch.autograd.Function):
                 dpart[pair[0]].copy_(d0)
                 dpart[pair[1]].copy_(d1)
             if order:
-                wgrad_into(dh[r], A["xln2"][r], _span(direct, order), [direct[n] for n in order])
+                wgrad_into(dh[r], A["xln2"][r], _span(direct, order), [direct[n] for n in order], ktiles=kts[i])
             else:
                 for n in pair:
                     if needs[n]:
-                        weight_grad(n, dpart[n], A["xln2"][r])
+                        weight_grad(n, dpart[n], A["xln2"][r], ktiles=kts[i])
         if fold is not None and needs["g2"] and not fused:  # the fp32 sum of temporaries (_return_grads folds it into a flat view),
             if "g2" in fold:                                   # or every segment accumulated in place
                 G["g2"] = fold["g2"].to(dt)
