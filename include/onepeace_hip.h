@@ -447,6 +447,28 @@ int op_image_resize_normalize(const void* src, int64_t src_bytes, const int64_t*
 int op_audio_normalize_pad(const void* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B, int64_t max_len,
                            int64_t min_len, void* out, int64_t T, int out_dtype, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- audio sample-rate conversion: polyphase Kaiser-windowed sinc (csrc/audioresample.hip) ------------------------------------
+ * Replaces the resampling of one_peace/models/one_peace/hub_interface.py:175 (librosa.load(audio, sr=16000): soxr on the host) for B
+ * decoded clips of different rates and lengths, in one launch.  The filter is this project's own, defined in closed form on the host
+ * (one-peace_amd/audioprep.py: resample_filter); it is NOT soxr's, so resampled audio differs from the reference's by the difference
+ * between the two low-pass filters.  Additive: op_abi_version() stays 10, no existing entry point changed.
+ * src: the clips in op_audio_normalize_pad's source layout (int16 PCM or fp32, 1 or 2 interleaved channels, clip i at the 16-aligned
+ * byte desc[i].src_off).  desc: int64 [B][12] per clip {src_off, frames, channels, format, L, M, T, half, coef_off, out_frames, dst_off,
+ * 0}, on the DEVICE; desc_host: the same table in HOST memory (validated here, sizes the launch).  The rate ratio is L / M in lowest
+ * terms, h[-half ... half] the low-pass at L times the input rate, T = floor(2 half / L) + 1 the taps per output and
+ * out_frames = ceil(frames L / M).  coef: fp32 tables built on the host; the clip's table starts at element coef_off (a multiple of 4)
+ * and holds L rows of Tp = 4 ceil(T / 4) taps: row p, tap t = fp32(L h[p + (floor((half - p) / L) - t) L]), 0 outside the filter and
+ * for t >= T.  Clips of the same rate share a table.
+ * out: clip i's mono fp32 samples at byte dst_off (a multiple of 16): op_audio_normalize_pad's source layout with format 1 and one
+ * channel.  out[n] = L sum_j x[j] h[n M - j L] over 0 <= j < frames, x = the channel mean (int16: s / 32768, (l + r) / 65536, exact;
+ * fp32 stereo: fl(l + r) * 0.5): Tp fp32 fused multiply-adds in four interleaved partial sums.  With S[n] = L sum_j |x[j] h[n M - j L]|,
+ * |out[n] - exact| <= (T + 3) 2^-24 S[n].  Nothing outside [0, frames) of a clip is read and nothing outside its out_frames samples
+ * written; n M is formed in 64 bits.  No atomics: two runs give the same bits, and a clip's values depend on nothing else in the batch.
+ * 1 <= frames, out_frames <= 2^27, channels 1 or 2, 1 <= L <= 640, L <= half, floor(255 M / L) + Tp + 2 <= 8192 (the input window of a
+ * workgroup's 256 outputs, staged in LDS), B <= 65535; src, coef, out 16-byte aligned; else OP_EINVAL before anything is launched. */
+int op_audio_resample(const void* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B, const float* coef,
+                      int64_t coef_count, void* out, int64_t out_bytes, void* stream);
+
 /* ---- classification metrics: average precision per class without a sort or a host copy (csrc/metrics.hip) ---------------------
  * Replaces the host path of the MAP metric (one_peace/metrics/map.py:35-44: torch.sigmoid(preds).cpu().numpy(), then sklearn's
  * average_precision_score(targets, preds, average=None): a device-to-host copy of [N, C] floats and one host sort per class).

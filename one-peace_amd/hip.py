@@ -89,6 +89,7 @@ SIGNATURES = {
     "op_sim_topk": (c_int, [P, I64, P, I64, I64, I64, I64, I64, P, P, P, I64, I64, P]),
     "op_image_resize_normalize": (c_int, [P, I64, P, P, I64, P, I64, I64, P, P, P, c_int, P, I64, P]),
     "op_audio_normalize_pad": (c_int, [P, I64, P, P, I64, I64, I64, P, I64, c_int, P, I64, P]),
+    "op_audio_resample": (c_int, [P, I64, P, P, I64, P, I64, P, I64, P]),
     "op_average_precision_workspace_bytes": (I64, [I64, I64]),
     "op_average_precision": (c_int, [P, I64, P, I64, I64, I64, P, P, P, I64, P]),
     "op_row_loss": (c_int, [P, c_int, I64, P, c_int, I64, I64, I64, c_int, c_float, c_float, c_float, P, P, P, P, P]),
@@ -1135,6 +1136,49 @@ def audio_normalize_pad(packed, dtype=torch.float32, device=None):
         base = buf.data_ptr()
         _check(lib().op_audio_normalize_pad(c_void_p(base), packed.src_bytes, c_void_p(base + packed.desc_off),
                                             packed.desc.ctypes.data_as(c_void_p), B, packed.max_len, packed.min_len, ptr(out), T,
+                                            DT_BF16 if dtype == torch.bfloat16 else DT_F32, ptr(ws), ws.numel(), stream()),
+               "op_audio_normalize_pad")
+    return out
+
+
+def audio_resample(packed, device=None):
+    """Run op_audio_resample on an audioprep.PackedResample batch: the packed host buffer (clips, descriptors, coefficient tables and,
+    where staged, the normaliser's descriptors) goes to the device in ONE copy.  Staged with norm=None it returns the resampled clips
+    as fp32 [B, rows] (row i zero behind packed.lengths[i]; the rows of clips already at the target rate stay zero, the caller owns
+    them).  Staged with norm=(max_len, min_len) it returns the uint8 device buffer of packed.total_bytes -- host part, then the
+    resampled mono fp32 clips at packed.out_off -- for audio_normalize_pad_device."""
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        buf = torch.empty(packed.total_bytes, dtype=torch.uint8, device=dev)
+        buf[:packed.host.numel()].copy_(packed.host, non_blocking=packed.host.is_pinned())
+        base = buf.data_ptr()
+        if packed.norm_desc is None:
+            out = torch.zeros((len(packed), packed.rows), dtype=torch.float32, device=dev)
+            out_ptr = out.data_ptr()
+        else:
+            out, out_ptr = buf, base + packed.out_off
+        if len(packed.which):
+            _check(lib().op_audio_resample(c_void_p(base), packed.src_bytes, c_void_p(base + packed.desc_off),
+                                           packed.desc.ctypes.data_as(c_void_p), len(packed.which), c_void_p(base + packed.coef_off),
+                                           packed.coef_count, c_void_p(out_ptr), packed.out_bytes, stream()), "op_audio_resample")
+    return out
+
+
+def audio_normalize_pad_device(buf, packed, dtype=torch.float32):
+    """audio_normalize_pad on a packed buffer that is already on the device: `buf` is audio_resample's buffer of a PackedResample staged
+    with norm=(max_len, min_len), whose normaliser descriptors point at the resampled clips (and at the staged source of clips that
+    needed no resampling).  No host round trip: op_audio_normalize_pad reads what op_audio_resample wrote, in stream order."""
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("audio_normalize_pad_device: dtype must be bfloat16 or float32, got %s" % dtype)
+    B, T = len(packed), packed.T
+    out = torch.empty((B, T), dtype=dtype, device=buf.device)
+    if B == 0:
+        return out
+    with torch.cuda.device(buf.device):
+        ws = torch.empty(max(packed.workspace_bytes, 16), dtype=torch.uint8, device=buf.device)
+        base = buf.data_ptr()
+        _check(lib().op_audio_normalize_pad(c_void_p(base), packed.total_bytes, c_void_p(base + packed.norm_desc_off),
+                                            packed.norm_desc.ctypes.data_as(c_void_p), B, packed.max_len, packed.min_len, ptr(out), T,
                                             DT_BF16 if dtype == torch.bfloat16 else DT_F32, ptr(ws), ws.numel(), stream()),
                "op_audio_normalize_pad")
     return out

@@ -2,9 +2,9 @@
 ``from_pretrained(...) -> OnePeaceHubInterface`` with ``extract_{text,image,audio,vl}_features`` (:206-225) and the dtype
 cast of :107-122.  ``process_image`` (:150-168) takes image files, PIL images or decoded uint8 arrays and runs the reference's
 transform (:94-101) -- on a device through the HIP resize kernel (ops.preprocess_images), bit for bit; ``process_text`` takes
-token ids (no BPE) and does the collation only; ``process_audio`` (:170-193) takes 16 kHz WAV files, int16 PCM or float waveforms
-(no librosa, no resampling) and runs layer norm, crop, tiling and padding through ops.preprocess_audio, on a device in
-op_audio_normalize_pad."""
+token ids (no BPE) and does the collation only; ``process_audio`` (:170-193) takes WAV files, int16 PCM or float waveforms (no
+librosa) and runs layer norm, crop, tiling and padding through ops.preprocess_audio, on a device in op_audio_normalize_pad; with
+``resample=True`` clips at another rate are first resampled with this project's own low-pass (op_audio_resample), not soxr's."""
 import os
 from types import SimpleNamespace
 
@@ -112,7 +112,7 @@ class OnePeaceHubInterface:
         normalisation run in op_image_resize_normalize (bit-identical to PIL + torchvision); on the CPU PIL does the resize.
         A floating-point tensor is taken as already pre-processed and only moved and cast, as before.
         Out of scope: JPEG / PNG decoding stays in PIL on the host; BPE for process_text, training-time augmentation
-        (RandomResizedCrop, RandAugment) and audio resampling (process_audio takes 16 kHz WAV files) are not provided."""
+        (RandomResizedCrop, RandAugment) are not provided."""
         from .. import ops
         if torch.is_tensor(image_list) or isinstance(image_list, np.ndarray):
             batch = torch.as_tensor(image_list)
@@ -154,14 +154,18 @@ class OnePeaceHubInterface:
             n = 1 + (n - (k - 1) - 1) // s
         return n
 
-    def process_audio(self, audio_list, sample_rate=16000):
+    def process_audio(self, audio_list, sample_rate=16000, resample=False):
         """hub_interface.py:170-193: (src_audios [B, T], audio_padding_masks [B, frames + 1]) of audio clips.  Items, mixed freely:
         paths of 16-bit PCM WAV files (audioprep.read_wav), int16 PCM [n] / [n, 2], or float [n] / [n, C] arrays or tensors.  Per
         clip: mean over the channels, layer norm over the whole clip, crop to 15 s, tiling up to 1 s, an all-False frame mask of the
         clip's OWN length; then right-padding of the waveforms with 0 and of the masks with True (built on the host).
-        A file whose rate is not `sample_rate` raises ValueError("sample rate: R, need 16000"), as data/base_dataset.py:88-89.
-        Resampling is not provided: the reference's librosa.load(sr=16000) resamples with soxr, which cannot be reproduced (or
-        tested) without librosa / soxr, and the reference's own datasets refuse other rates as well.
+        An item may also be a (clip, rate) pair.  With resample=False a file or pair whose rate is not `sample_rate` raises
+        ValueError("sample rate: R, need 16000"), as data/base_dataset.py:88-89.  With resample=True it is resampled first, as the
+        reference's librosa.load(sr=16000) does (:175) -- but with the Kaiser-windowed sinc of audioprep.resample_filter
+        (ops.resample_audio; on a device op_audio_resample, handed to the normalise kernel without leaving the device), not with
+        librosa's soxr, which is not reproduced here: features of resampled audio differ from the reference's by the difference
+        between the two low-pass filters.  The layer norm runs over the whole resampled clip before the crop (:176-182), and the
+        frame masks come from the resampled lengths.  Clips at `sample_rate` are computed exactly as with resample=False.
         With device="cpu" this is ops.preprocess_audio's torch route, bit for bit what this method computed for 1-D float
         waveforms before it took files.  On a GPU device the same inputs go through op_audio_normalize_pad (csrc/audioprep.hip)
         and may differ from the host route by rounding: each fp32 value is within 2^-24 (4 |y| + 2 |mean| rstd) of the fp64
@@ -169,7 +173,7 @@ class OnePeaceHubInterface:
         hub dtype."""
         from .. import ops
         kdt = self.dtype if self.dtype in (torch.bfloat16, torch.float32) else torch.float32
-        wavs, lengths = ops.preprocess_audio(audio_list, sample_rate, 15, 1, dtype=kdt, device=self.device)
+        wavs, lengths = ops.preprocess_audio(audio_list, sample_rate, 15, 1, dtype=kdt, device=self.device, resample=resample)
         frames = [self._frames(int(n)) + 1 for n in lengths]
         pad = torch.ones(len(frames), max(frames, default=0), dtype=torch.bool)
         for i, f in enumerate(frames):

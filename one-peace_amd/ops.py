@@ -601,22 +601,89 @@ def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, de
 # --------------------------------------------------------------------------------------------------------------
 # audio pre-processing: base_dataset.py:84-102 / hub_interface.py:170-193 (layer norm, crop, tile, pad) on decoded clips
 # --------------------------------------------------------------------------------------------------------------
-def preprocess_audio(clips, sample_rate=16000, max_seconds=15, min_seconds=1, dtype=torch.float32, device="cpu"):
-    """(wavs [B, T] in `dtype` on `device`, lengths int64 [B] on the host) from audio clips: WAV paths at `sample_rate`, int16 PCM
-    [n] / [n, 2] or float [n] / [n, C] arrays or tensors, mixed freely.  Per clip: mean over the channels, F.layer_norm over the
-    whole clip, crop to sample_rate * max_seconds samples, a clip shorter than sample_rate * min_seconds repeated up to that length;
-    then right-padding with zeros to the longest clip T (`lengths` are the samples before the padding).  On a CUDA device this is
-    op_audio_normalize_pad (hip.audio_normalize_pad: one H2D copy of the staged samples, statistics in integers / fp64, each value
-    within 2^-24 (4 |y| + 2 |mean| rstd) of the fp64 result); on the CPU it is audioprep.postprocess, the reference's own torch
-    arithmetic.  No resampling: a file at another rate is a ValueError."""
+def _audio_item(item, sample_rate, resample):
+    """(as_clip array, rate) of one input of preprocess_audio / resample_audio: a WAV path (the file's rate), a (clip, rate) pair, or a
+    clip taken to be at `sample_rate`.  Without `resample` another rate is audioprep.check_rate's ValueError."""
+    import os
+
+    import numpy as np
+
     from . import audioprep
-    arrs = [audioprep.as_clip(c, sample_rate) for c in clips]
+    rate = sample_rate
+    if isinstance(item, tuple) and len(item) == 2 and (torch.is_tensor(item[0]) or isinstance(item[0], (np.ndarray, list, str, bytes, os.PathLike))):
+        item, rate = item
+        audioprep._check_rates(rate, sample_rate)
+    if isinstance(item, (str, bytes, os.PathLike)):
+        item, rate = audioprep.read_wav(item)
+    if not resample:
+        audioprep.check_rate(rate, sample_rate)
+    return audioprep.as_clip(item), int(rate)
+
+
+def resample_audio(clips, rates, sample_rate=16000, device="cpu"):
+    """(wavs fp32 [B, Tmax] on `device`, lengths int64 [B] on the host): each clip (int16 PCM [n] / [n, 2] or float [n] / [n, C]) brought
+    from its rate to `sample_rate` and to mono, zero-padded to the longest.  The filter is audioprep.resample_filter's Kaiser-windowed
+    sinc, y[n] = L sum_j x[j] h[n M - j L] with zeros outside the clip, ceil(n L / M) samples: scipy.signal.resample_poly(x, L, M,
+    window=h), NOT librosa's soxr -- results differ from the reference's by the difference between the two low-pass filters.  On a
+    CUDA device this is op_audio_resample (hip.audio_resample: one H2D copy of samples, descriptors and fp32 taps; each value within
+    (T + 3) 2^-24 L sum_j |x[j] h[n M - j L]| of the exact one); on the CPU it is audioprep.resample, accumulated in fp64 and rounded
+    once.  A clip already at `sample_rate` is not filtered: its mono fp32 samples pass through."""
+    import numpy as np
+
+    from . import audioprep
+    if len(rates) != len(clips):
+        raise ValueError("resample_audio: %d clips and %d rates" % (len(clips), len(rates)))
+    arrs = [audioprep.as_clip(c) for c in clips]
+    for r in rates:
+        audioprep._check_rates(r, sample_rate)
+    dev = torch.device(device)
+    same = [int(r) == int(sample_rate) for r in rates]
+    if dev.type == "cuda":
+        packed = audioprep.pack_resample(arrs, rates, sample_rate)
+        lengths = packed.lengths
+        wavs = hip.audio_resample(packed, dev)
+        for i, a in enumerate(arrs):
+            if same[i]:
+                wavs[i, : lengths[i]] = torch.from_numpy(audioprep.mono64(a).astype(np.float32)).to(dev)
+        wavs = wavs[:, : max(lengths, default=0)]
+    else:
+        feats = [audioprep.mono64(a).astype(np.float32) if same[i] else audioprep.resample(a, int(rates[i]), int(sample_rate))
+                 for i, a in enumerate(arrs)]
+        lengths = [w.shape[0] for w in feats]
+        wavs = torch.zeros(len(feats), max(lengths, default=0))
+        for i, w in enumerate(feats):
+            wavs[i, : lengths[i]] = torch.from_numpy(w)
+        wavs = wavs.to(dev)
+    return wavs, torch.tensor(lengths, dtype=torch.int64)
+
+
+def preprocess_audio(clips, sample_rate=16000, max_seconds=15, min_seconds=1, dtype=torch.float32, device="cpu", resample=False):
+    """(wavs [B, T] in `dtype` on `device`, lengths int64 [B] on the host) from audio clips: WAV paths, int16 PCM [n] / [n, 2] or float
+    [n] / [n, C] arrays or tensors at `sample_rate`, or (clip, rate) pairs, mixed freely.  Per clip: mean over the channels,
+    F.layer_norm over the whole clip, crop to sample_rate * max_seconds samples, a clip shorter than sample_rate * min_seconds repeated
+    up to that length; then right-padding with zeros to the longest clip T (`lengths` are the samples before the padding).  On a CUDA
+    device this is op_audio_normalize_pad (hip.audio_normalize_pad: one H2D copy of the staged samples, statistics in integers / fp64,
+    each value within 2^-24 (4 |y| + 2 |mean| rstd) of the fp64 result); on the CPU it is audioprep.postprocess, the reference's own
+    torch arithmetic.  resample=False: a file or pair at another rate is a ValueError.  resample=True: such a clip is first resampled
+    as by resample_audio (this project's Kaiser-windowed sinc, not the reference's soxr), and the layer norm runs over the whole
+    resampled clip before the crop; on a device that is op_audio_resample, then op_audio_normalize_pad reading the resampled clips
+    from the device buffer, with no host round trip.  Clips at `sample_rate` are computed exactly as with resample=False."""
+    from . import audioprep
+    items = [_audio_item(c, sample_rate, resample) for c in clips]
+    arrs, rates = [a for a, _ in items], [r for _, r in items]
     max_len, min_len = int(sample_rate * max_seconds), int(sample_rate * min_seconds)
     dev = torch.device(device)
+    other = any(r != int(sample_rate) for r in rates)
     if dev.type == "cuda":
-        packed = audioprep.pack_clips(arrs, max_len, min_len)
         kdt = dtype if dtype in (torch.bfloat16, torch.float32) else torch.float32
+        if other:
+            packed = audioprep.pack_resample(arrs, rates, sample_rate, norm=(max_len, min_len))
+            wavs = hip.audio_normalize_pad_device(hip.audio_resample(packed, dev), packed, kdt)
+            return wavs.to(dtype), torch.tensor(packed.out_lengths, dtype=torch.int64)
+        packed = audioprep.pack_clips(arrs, max_len, min_len)
         return hip.audio_normalize_pad(packed, kdt, dev).to(dtype), torch.tensor(packed.lengths, dtype=torch.int64)
+    if other:
+        arrs = [a if r == int(sample_rate) else audioprep.resample(a, r, int(sample_rate)) for a, r in items]
     feats = [audioprep.postprocess(a, sample_rate, max_seconds, min_seconds) for a in arrs]
     wavs = torch.zeros(len(feats), max([w.numel() for w in feats], default=0))
     for i, w in enumerate(feats):
