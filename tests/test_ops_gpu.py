@@ -4,7 +4,13 @@ Tolerances are the ones stated in tests/util.py.
 The GEMM tests here reach the launch routes with ONE input family, an fp32 reference and aggregate gates (relative Frobenius norm and
 largest error over the largest entry).  The per-element check of the same kernels against fp64 -- every route asserted by name, hard
 input families, outputs in guarded buffers -- is tests/test_gemm_fp64_gpu.py (reference, budget and cases: tests/gemm_ref.py, checked
-on the CPU by tests/test_gemm_ref_cpu.py)."""
+on the CPU by tests/test_gemm_ref_cpu.py).
+
+The LayerNorm tests here (test_layernorm_*, test_ln_geglu_*, the x_rows tests) stay below the row counts at which a row group takes a
+second row and use the same aggregate gates.  The per-element check of those kernels against fp64 -- the persistent row loop at three
+trips, mean and rstd as fp32 numbers, `add`, `accumulate`, the row table, the fp8 copies and the non-temporal variants, outputs in
+guarded buffers -- is tests/test_ln_fp64_gpu.py (reference, derived budget and cases: tests/ln_ref.py, checked on the CPU by
+tests/test_ln_ref_cpu.py)."""
 import math
 
 import pytest
