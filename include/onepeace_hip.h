@@ -364,6 +364,21 @@ int op_adamw_step_groups(void* p, const void* g, float* m, float* v, int64_t num
                          const float* group_lr_scale, const float* group_weight_decay, int64_t n_groups, float lr, float beta1,
                          float beta2, float eps, int64_t step, float grad_scale, const float* grad_sqnorm, float clip_norm,
                          void* stream);
+/* op_adamw_step_groups with an fp32 master copy of the parameters: the reference's `bf16: true` with `memory_efficient_bf16: false`,
+ * where trainer.py:297-307 selects FP16Optimizer (one_peace/optim/fp16_optimizer.py).  There build_fp32_params makes a flat fp32
+ * copy of the parameters, _sync_fp16_grads_to_fp32 widens the bf16 gradients, clip_grad_norm folds the clip coefficient into a
+ * factor the fp32 gradients are multiplied by, step runs Adam on the fp32 copy and _sync_fp32_params_to_fp16 casts it back to
+ * bf16.  Here: master (fp32 [numel], device) is read in the place of float(p), updated by the same expressions and stored; p
+ * (bf16) is only WRITTEN, with the round-to-nearest-even bf16 of the master value just stored; m, v, g, the group tables, grad_scale
+ * and the clip handling are those of op_adamw_step_groups.  28 B/param of traffic instead of 22, 4 B/param more memory.
+ * Clip ordering: in this arrangement the reference itself scales FP32 gradients by the clip coefficient, so the in-kernel fp32
+ * scaling is the reference's own order here -- not the deviation one-peace_amd/optim.py documents for the memory-efficient path
+ * (where the reference rounds the clipped gradient to bf16 first).
+ * Same argument checks as op_adamw_step_groups, and master != NULL.  Additive: op_abi_version() stays 10. */
+int op_adamw_step_groups_master(void* p, float* master, const void* g, float* m, float* v, int64_t numel,
+                                const int64_t* group_end8, const float* group_lr_scale, const float* group_weight_decay,
+                                int64_t n_groups, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
+                                const float* grad_sqnorm, float clip_norm, void* stream);
 /* out[0] = sum of squares of a bf16 vector in fp32 (the global gradient norm of fairseq/fairseq/utils.py:349-391 over the
  * flat gradient buffer; feeds op_adamw_step's device-side clip coefficient, trainer.py:929).  workspace: 1024 floats. */
 int op_sqnorm(const void* x, int64_t numel, float* workspace, float* out, void* stream);

@@ -534,6 +534,64 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(bf16_t* __restrict__ 
   }
 }
 
+// The same update with an fp32 master copy of the parameters (the reference's `bf16: true` without `memory_efficient_bf16`:
+// trainer.py:297-307 -> optim/fp16_optimizer.py: Adam runs on fp32_params, _sync_fp32_params_to_fp16 casts them back).  The
+// master takes the place of float(p): it is read, updated with the expressions of adamw_groups_kernel and stored in fp32, and p
+// receives the round-to-nearest-even bf16 of the value just stored.  p is never read, so an update below half a bf16 spacing
+// accumulates in the master instead of being rounded away every step.
+// Algorithmic bytes: 28 B/param (master r+w 8, g r 2, m and v r+w 16, p w 2).  Group lookup and non-finite behaviour as above.
+__global__ __launch_bounds__(256) void adamw_groups_master_kernel(bf16_t* __restrict__ p, float* __restrict__ master,
+                                                                  const bf16_t* __restrict__ g, float* __restrict__ m,
+                                                                  float* __restrict__ v, int64_t n8,
+                                                                  const int64_t* __restrict__ end8,
+                                                                  const float* __restrict__ lr_scale, const float* __restrict__ wd,
+                                                                  int n_groups, float lr, float beta1, float beta2, float eps,
+                                                                  float bias_corr, float grad_scale,
+                                                                  const float* __restrict__ sqnorm, float clip_norm) {
+  __shared__ int64_t s_end[ADAM_MAX_GROUPS];
+  __shared__ float s_step[ADAM_MAX_GROUPS], s_decay[ADAM_MAX_GROUPS];
+  for (int i = threadIdx.x; i < n_groups; i += 256) {
+    const float lr_g = lr * lr_scale[i];
+    s_end[i] = end8[i];
+    s_step[i] = lr_g * bias_corr;
+    s_decay[i] = 1.f - wd[i] * lr_g;
+  }
+  __syncthreads();
+  grad_scale = clipped_grad_scale(grad_scale, sqnorm, clip_norm);
+  int grp = 0;
+  int64_t lo = 0, hi = s_end[0];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+    if (i < lo || i >= hi) {  // first group whose end is > i
+      int a = 0, b = n_groups - 1;
+      while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (s_end[mid] > i) b = mid; else a = mid + 1;
+      }
+      grp = a;
+      lo = grp ? s_end[grp - 1] : 0;
+      hi = s_end[grp];
+    }
+    const float step_size = s_step[grp], decay_mul = s_decay[grp];
+    float pv[8], gv[8], mv[8], vv[8];
+    Vec8<float>::load(master + i * 8, pv);
+    Vec8<bf16_t>::load(g + i * 8, gv);
+    Vec8<float>::load(m + i * 8, mv);
+    Vec8<float>::load(v + i * 8, vv);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float gr = gv[j] * grad_scale;
+      mv[j] = mv[j] * beta1 + (1.f - beta1) * gr;
+      vv[j] = vv[j] * beta2 + (1.f - beta2) * gr * gr;
+      const float denom = sqrtf(vv[j]) + eps;
+      pv[j] = pv[j] * decay_mul - step_size * (mv[j] / denom);
+    }
+    Vec8<float>::store(master + i * 8, pv);
+    Vec8<bf16_t>::store(p + i * 8, pv);  // bf16(master'), round to nearest even: the reference's _sync_fp32_params_to_fp16
+    Vec8<float>::store(m + i * 8, mv);
+    Vec8<float>::store(v + i * 8, vv);
+  }
+}
+
 // sum of squares, stage 1: one partial per workgroup (grid-stride over 8-element vectors); stage 2 folds the partials
 __global__ __launch_bounds__(256) void sqnorm_partial_kernel(const bf16_t* __restrict__ x, int64_t n8, float* __restrict__ part) {
   __shared__ float red[4];
@@ -1037,6 +1095,25 @@ int op_adamw_step_groups(void* p, const void* g, float* m, float* v, int64_t num
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   hipLaunchKernelGGL(adamw_groups_kernel, dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p,
+                     (const bf16_t*)g, m, v, numel / 8, group_end8, group_lr_scale, group_weight_decay, (int)n_groups, lr, beta1,
+                     beta2, eps, (float)(sqrt(bc2) / bc1), grad_scale, grad_sqnorm, clip_norm);
+  OP_LAUNCH_CHECK();
+  return OP_OK;
+}
+
+// op_adamw_step_groups with an fp32 master copy (include/onepeace_hip.h): master is read and written, p only written
+// (= bf16(master)), 28 B/param.  Same tables, clip handling and argument checks, plus master != NULL.
+int op_adamw_step_groups_master(void* p, float* master, const void* g, float* m, float* v, int64_t numel,
+                                const int64_t* group_end8, const float* group_lr_scale, const float* group_weight_decay,
+                                int64_t n_groups, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
+                                const float* grad_sqnorm, float clip_norm, void* stream) {
+  OP_CHECK_ARG(p && master && g && m && v && group_end8 && group_lr_scale && group_weight_decay, "adamw_groups_master: null pointer");
+  OP_CHECK_ARG(numel % 8 == 0 && step >= 1 && n_groups >= 1 && n_groups <= ADAM_MAX_GROUPS,
+               "adamw_groups_master: numel %% 8 == 0, step >= 1, 1 <= n_groups <= %d required", ADAM_MAX_GROUPS);
+  if (numel == 0) return OP_OK;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  hipLaunchKernelGGL(adamw_groups_master_kernel, dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p, master,
                      (const bf16_t*)g, m, v, numel / 8, group_end8, group_lr_scale, group_weight_decay, (int)n_groups, lr, beta1,
                      beta2, eps, (float)(sqrt(bc2) / bc1), grad_scale, grad_sqnorm, clip_norm);
   OP_LAUNCH_CHECK();

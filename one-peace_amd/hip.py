@@ -67,6 +67,8 @@ SIGNATURES = {
     "op_infonce_rows": (c_int, [P, I64, I64, I64, I64, c_float, c_float, P, P, P, c_int, P]),
     "op_adamw_step": (c_int, [P, P, P, P, I64, c_float, c_float, c_float, c_float, c_float, I64, c_float, P, c_float, P]),
     "op_adamw_step_groups": (c_int, [P, P, P, P, I64, P, P, P, I64, c_float, c_float, c_float, c_float, I64, c_float, P, c_float, P]),
+    "op_adamw_step_groups_master": (c_int, [P, P, P, P, P, I64, P, P, P, I64, c_float, c_float, c_float, c_float, I64, c_float, P,
+                                           c_float, P]),
     "op_sqnorm": (c_int, [P, I64, P, P, P]),
     "op_relpos_bias_build": (c_int, [P, P, I64, P, I64, I64, I64, c_int, P]),
     "op_relpos_bias_bwd": (c_int, [P, I64, I64, P, P, I64, P, I64, P, P, I64, P]),
@@ -799,6 +801,15 @@ def adamw_step_groups(p, g, m, v, group_end8, group_lr_scale, group_wd, lr, beta
     _check(lib().op_adamw_step_groups(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(group_end8), ptr(group_lr_scale),
                                       ptr(group_wd), group_end8.numel(), lr, beta1, beta2, eps, step, grad_scale, ptr(grad_sqnorm),
                                       clip_norm, stream()), "op_adamw_step_groups")
+
+
+def adamw_step_groups_master(p, master, g, m, v, group_end8, group_lr_scale, group_wd, lr, beta1, beta2, eps, step, grad_scale=1.0,
+                             grad_sqnorm=None, clip_norm=0.0):
+    """adamw_step_groups with an fp32 master copy: `master` (fp32, as long as p) is read and updated, the bf16 `p` is only written,
+    as the round-to-nearest-even cast of the new master."""
+    _check(lib().op_adamw_step_groups_master(ptr(p), ptr(master), ptr(g), ptr(m), ptr(v), p.numel(), ptr(group_end8),
+                                             ptr(group_lr_scale), ptr(group_wd), group_end8.numel(), lr, beta1, beta2, eps, step,
+                                             grad_scale, ptr(grad_sqnorm), clip_norm, stream()), "op_adamw_step_groups_master")
 
 
 def sqnorm(x, out=None):

@@ -1,15 +1,25 @@
 """Fused AdamW over flat bf16 parameters.
 
-Update rule = the reference's in-repo ``Adam`` (one_peace/optim/adam.py:186-253; what runs when apex is absent):
-fp32 moments, fp32 math on bf16 parameters (the ``MemoryEfficientFP16Optimizer`` arrangement: no fp32 master copy),
-decoupled weight decay applied before the Adam update, eps added to sqrt(v).  Param groups = the reference's
+Update rule = the reference's in-repo ``Adam`` (one_peace/optim/adam.py:186-253; what runs when apex is absent): fp32 moments, fp32
+math, decoupled weight decay applied before the Adam update, eps added to sqrt(v).  Param groups = the reference's
 (trainer.py:265-278 -> utils/layer_decay.py:34-77): no weight decay for ``ndim <= 1`` / ``.bias`` / ``no_weight_decay()`` names,
 and -- with ``layer_decay < 1`` -- the lr of layer id i scaled by ``layer_decay ** (L + 1 - i)`` (optim/base_optimizer.py:8-14).
 ONE HIP launch over the flat buffers of ``distributed.FlatParameters`` per step, whatever the number of groups (a device table
-maps ranges to their lr scale / weight decay): 22 bytes/parameter of HBM traffic.
+maps ranges to their lr scale / weight decay).
 
-Deviation from the reference, stated: global-norm clipping multiplies the gradient by the clip coefficient in fp32 inside the
-update kernel; the reference scales its bf16 gradients in place first (fairseq/utils.py:393-397: one extra bf16 rounding)."""
+Two arrangements of the bf16 parameters, as the reference has them (trainer.py:297-307):
+
+  * ``master_weights=False`` (default) -- ``MemoryEfficientFP16Optimizer`` (``memory_efficient_bf16: true``): the parameters exist in
+    bf16 only; the step widens them to fp32, updates and rounds straight back.  22 bytes/parameter of HBM traffic.  An update
+    smaller than half a bf16 spacing (2^-9 |p|) is rounded away, every step, and never accumulates.
+  * ``master_weights=True`` -- ``FP16Optimizer`` (``bf16: true`` alone; optim/fp16_optimizer.py:13-250): a flat fp32 master copy is
+    what Adam updates, and the bf16 parameters are its cast after every step.  28 bytes/parameter of traffic and +4 bytes/parameter
+    of memory: +15.6 GB at the 4B model, against 267 of 309 GB reserved at the headline batch.
+
+Deviation from the reference, stated, for the memory-efficient arrangement only: global-norm clipping multiplies the gradient by
+the clip coefficient in fp32 inside the update kernel; the reference scales its bf16 gradients in place first
+(fairseq/utils.py:393-397: one extra bf16 rounding).  With master weights the reference itself multiplies fp32 gradients
+(fp16_optimizer.py: _sync_fp16_grads_to_fp32, clip_grad_norm, _unscale_grads), so there the kernel's order is the reference's."""
 import re
 
 import torch
@@ -49,10 +59,16 @@ def reference_param_groups(model, num_layers=None, layer_decay=1.0):
 
 
 class FusedAdamW:
-    def __init__(self, flat: FlatParameters, lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.05):
+    """master_weights=True keeps ``self.master``, an fp32 copy of ``flat.params`` taken at construction: the step updates the master
+    and writes ``flat.params`` as its bf16 cast, without reading it.  Anything written into ``flat.params`` from outside afterwards
+    (weights loaded into the model once the optimiser exists) must be followed by ``sync_master()``: otherwise the next step
+    overwrites it with the cast of the old master."""
+
+    def __init__(self, flat: FlatParameters, lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.05, master_weights=False):
         if not flat.params.is_cuda or flat.params.dtype != torch.bfloat16:
             raise RuntimeError("FusedAdamW needs bf16 parameters on an MI355X (the HIP path has no CPU fallback)")
         self.flat = flat
+        self.master = flat.params.float() if master_weights else None
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros(flat.numel, dtype=torch.float32, device=flat.params.device)
         self.exp_avg_sq = torch.zeros_like(self.exp_avg)
@@ -68,6 +84,12 @@ class FusedAdamW:
         """optim/base_optimizer.py:8-14: the scheduled lr; group g runs at lr * lr_scale_g."""
         self.lr = lr
 
+    def sync_master(self):
+        """Re-read the fp32 master from ``flat.params`` (fp16_optimizer.py: build_fp32_params, after an outside write)."""
+        if self.master is None:
+            raise RuntimeError("sync_master: this optimiser was built without master_weights")
+        self.master.copy_(self.flat.params)
+
     def step(self, grad_scale=1.0, clip_norm=0.0):
         """grad_scale multiplies the gradient inside the kernel (1/world_size after a SUM all-reduce, trainer.py:917-923).
         clip_norm > 0: the reference's global-norm clipping (trainer.py:929 -> fairseq/utils.py:349-397) -- the norm is
@@ -80,8 +102,13 @@ class FusedAdamW:
         self.step_count += 1
         f = self.flat
         sq = hip.sqnorm(f.grads) if clip_norm > 0 else None
-        hip.adamw_step_groups(f.params, f.grads, self.exp_avg, self.exp_avg_sq, self._end8, self._scale, self._wd, self.lr,
-                              self.betas[0], self.betas[1], self.eps, self.step_count, grad_scale, sq, clip_norm)
+        if self.master is None:
+            hip.adamw_step_groups(f.params, f.grads, self.exp_avg, self.exp_avg_sq, self._end8, self._scale, self._wd, self.lr,
+                                  self.betas[0], self.betas[1], self.eps, self.step_count, grad_scale, sq, clip_norm)
+        else:
+            hip.adamw_step_groups_master(f.params, self.master, f.grads, self.exp_avg, self.exp_avg_sq, self._end8, self._scale,
+                                         self._wd, self.lr, self.betas[0], self.betas[1], self.eps, self.step_count, grad_scale, sq,
+                                         clip_norm)
         ops.refresh_weight_cache()  # the raw-pointer update does not bump _version: refresh the dgrad copies in one launch
         return sq.sqrt() * abs(grad_scale) if sq is not None else None
 
@@ -92,10 +119,12 @@ class FusedAdamW:
 class TorchAdamW:
     """The same update over ``FlatParameters`` written with torch ops (fp32 math on the flat buffers, any device / dtype): the
     optimiser of the CPU control-flow runs of the data-parallel step (``bench.py --debug-cpu-micro``, world-size-4 gloo test) and
-    a readable statement of what the fused kernel computes.  Same interface as ``FusedAdamW``."""
+    a readable statement of what the fused kernel computes.  Same interface as ``FusedAdamW``, ``master_weights`` included: with
+    it the fp32 ``self.master`` is what the rule reads and writes, and ``flat.params`` receives its cast."""
 
-    def __init__(self, flat: FlatParameters, lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.05):
+    def __init__(self, flat: FlatParameters, lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.05, master_weights=False):
         self.flat = flat
+        self.master = flat.params.float() if master_weights else None
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros(flat.numel, dtype=torch.float32, device=flat.params.device)
         self.exp_avg_sq = torch.zeros_like(self.exp_avg)
@@ -104,12 +133,21 @@ class TorchAdamW:
     def set_lr(self, lr):
         self.lr = lr
 
+    def sync_master(self):
+        if self.master is None:
+            raise RuntimeError("sync_master: this optimiser was built without master_weights")
+        self.master.copy_(self.flat.params)
+
     @torch.no_grad()
     def step(self, grad_scale=1.0, clip_norm=0.0):
         self.step_count += 1
         f, (b1, b2) = self.flat, self.betas
         g = f.grads.float() * grad_scale
         norm = g.norm() if clip_norm > 0 else None
+        if norm is not None and self.master is not None:
+            # a flat fp32 norm over millions of elements is off by up to ~4e-4 relative on the CPU; the bf16 rounding of the other
+            # arrangement hides that, an fp32 master does not (the reference sums per-parameter norms): accumulate in fp64
+            norm = torch.linalg.vector_norm(g, dtype=torch.float64).float()
         if norm is not None:
             g = g * (clip_norm / (norm + 1e-6)).clamp(max=1.0)  # fairseq/utils.py:349-397
         self.exp_avg.mul_(b1).add_(g, alpha=1 - b1)
@@ -119,10 +157,14 @@ class TorchAdamW:
         for start, end, scale, decays in f.groups:
             if end <= start:
                 continue
-            pf = f.params[start:end].float()
+            pf = f.params[start:end].float() if self.master is None else self.master[start:end]
             if decays and self.weight_decay != 0:
                 pf = pf + pf * (-self.weight_decay * self.lr * scale)
-            f.params[start:end].copy_(pf - self.lr * scale * bias * update[start:end])
+            new = pf - self.lr * scale * bias * update[start:end]
+            if self.master is not None:
+                self.master[start:end].copy_(new)
+                new = self.master[start:end].to(f.params.dtype)
+            f.params[start:end].copy_(new)
         if f.params.is_cuda:
             ops.refresh_weight_cache()
         return norm
