@@ -379,6 +379,22 @@ int op_adamw_step_groups_master(void* p, float* master, const void* g, float* m,
                                 const int64_t* group_end8, const float* group_lr_scale, const float* group_weight_decay,
                                 int64_t n_groups, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
                                 const float* grad_sqnorm, float clip_norm, void* stream);
+/* One step of the exponential moving average of the weights, kept in fp32 (the reference's EMAModule with `ema_fp32: true`,
+ * trainer.py:243-250 and :895-907; the averaging rule is fairseq/modules/ema_module.py:101-127): for every element
+ *     ema = fmaf(take, float(p), fl32(keep * ema))        keep = float(decay), take = float(1.0 - decay)
+ * with the product and the fma rounded separately -- bit for bit torch's `ema.mul_(decay); ema.add_(p.float(), alpha=1 - decay)`.
+ * ema: fp32 [numel], read and written; p: bf16 [numel], only read.  keep = 0, take = 1 copies p (updates < ema_start_update).
+ * numel % 8 == 0.  10 B/param.  Additive: op_abi_version() stays 10. */
+int op_ema_step(float* ema, const void* p, int64_t numel, float keep, float take, void* stream);
+/* op_adamw_step_groups (master == NULL) or op_adamw_step_groups_master (master != NULL), and op_ema_step on the parameters that
+ * step stores, in ONE launch: p, master, m and v receive bit for bit what the unfused entry gives, ema what op_ema_step gives from
+ * the new bf16 p (never from the master: the reference's EMA reads the model).  30 B/param without the master, 36 with it, against
+ * 22 + 10 and 28 + 10 for the pair.  Argument checks of op_adamw_step_groups, and ema != NULL; ema must not overlap master.
+ * Additive: op_abi_version() stays 10. */
+int op_adamw_step_groups_ema(void* p, float* master, const void* g, float* m, float* v, float* ema, int64_t numel,
+                             const int64_t* group_end8, const float* group_lr_scale, const float* group_weight_decay,
+                             int64_t n_groups, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
+                             const float* grad_sqnorm, float clip_norm, float ema_keep, float ema_take, void* stream);
 /* out[0] = sum of squares of a bf16 vector in fp32 (the global gradient norm of fairseq/fairseq/utils.py:349-391 over the
  * flat gradient buffer; feeds op_adamw_step's device-side clip coefficient, trainer.py:929).  workspace: 1024 floats. */
 int op_sqnorm(const void* x, int64_t numel, float* workspace, float* out, void* stream);

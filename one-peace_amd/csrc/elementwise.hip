@@ -592,6 +592,94 @@ __global__ __launch_bounds__(256) void adamw_groups_master_kernel(bf16_t* __rest
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// Exponential moving average of the weights in fp32 (the reference's EMAModule with ema_fp32: true; the rule is the one of
+// fairseq/modules/ema_module.py:101-127: ema.mul_(decay); ema.add_(param.to(ema.dtype), alpha=1 - decay)):
+//   e' = fmaf(take, p, fl32(keep * e))       keep = float(decay), take = float(1 - decay), p the bf16 parameter as stored
+// which is bit for bit what torch computes for the two lines on a CPU.  The product and the fma are written out and contraction is
+// switched off around them, so no compiler setting turns the two roundings into another pair.  keep = 0, take = 1 gives e' = p.
+// ------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float ema_rule(float e, float p, float keep, float take) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(take, p, __fmul_rn(keep, e));
+}
+
+// The stand-alone pass.  Algorithmic bytes: 10 B/param (e r+w 8, p r 2).
+__global__ __launch_bounds__(256) void ema_step_kernel(float* __restrict__ e, const bf16_t* __restrict__ p, int64_t n8, float keep,
+                                                       float take) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+    float ev[8], pv[8];
+    Vec8<float>::load(e + i * 8, ev);
+    Vec8<bf16_t>::load(p + i * 8, pv);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ev[j] = ema_rule(ev[j], pv[j], keep, take);
+    Vec8<float>::store(e + i * 8, ev);
+  }
+}
+
+// adamw_groups_kernel (MASTER = false) / adamw_groups_master_kernel (MASTER = true) with the EMA pass folded in: the same
+// expressions in the same order for p, master, m and v, one more fp32 stream e, and after the update the rule above with the value
+// the bf16 store of p rounds to -- also with a master: the reference's EMA reads the model, never the optimiser's fp32 copy.
+// Algorithmic bytes: 30 B/param without the master (22 + e r+w 8), 36 B/param with it (28 + 8).  Group lookup and non-finite
+// behaviour as above; a NaN clip coefficient makes every parameter NaN and with it every element of e.
+template <bool MASTER>
+__global__ __launch_bounds__(256) void adamw_groups_ema_kernel(bf16_t* __restrict__ p, float* __restrict__ master,
+                                                               const bf16_t* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, float* __restrict__ e, int64_t n8,
+                                                               const int64_t* __restrict__ end8,
+                                                               const float* __restrict__ lr_scale, const float* __restrict__ wd,
+                                                               int n_groups, float lr, float beta1, float beta2, float eps,
+                                                               float bias_corr, float grad_scale,
+                                                               const float* __restrict__ sqnorm, float clip_norm, float keep,
+                                                               float take) {
+  __shared__ int64_t s_end[ADAM_MAX_GROUPS];
+  __shared__ float s_step[ADAM_MAX_GROUPS], s_decay[ADAM_MAX_GROUPS];
+  for (int i = threadIdx.x; i < n_groups; i += 256) {
+    const float lr_g = lr * lr_scale[i];
+    s_end[i] = end8[i];
+    s_step[i] = lr_g * bias_corr;
+    s_decay[i] = 1.f - wd[i] * lr_g;
+  }
+  __syncthreads();
+  grad_scale = clipped_grad_scale(grad_scale, sqnorm, clip_norm);
+  int grp = 0;
+  int64_t lo = 0, hi = s_end[0];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+    if (i < lo || i >= hi) {  // first group whose end is > i
+      int a = 0, b = n_groups - 1;
+      while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (s_end[mid] > i) b = mid; else a = mid + 1;
+      }
+      grp = a;
+      lo = grp ? s_end[grp - 1] : 0;
+      hi = s_end[grp];
+    }
+    const float step_size = s_step[grp], decay_mul = s_decay[grp];
+    float pv[8], gv[8], mv[8], vv[8], ev[8];
+    if constexpr (MASTER) Vec8<float>::load(master + i * 8, pv);
+    else Vec8<bf16_t>::load(p + i * 8, pv);
+    Vec8<bf16_t>::load(g + i * 8, gv);
+    Vec8<float>::load(m + i * 8, mv);
+    Vec8<float>::load(v + i * 8, vv);
+    Vec8<float>::load(e + i * 8, ev);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float gr = gv[j] * grad_scale;
+      mv[j] = mv[j] * beta1 + (1.f - beta1) * gr;
+      vv[j] = vv[j] * beta2 + (1.f - beta2) * gr * gr;
+      const float denom = sqrtf(vv[j]) + eps;
+      pv[j] = pv[j] * decay_mul - step_size * (mv[j] / denom);
+      ev[j] = ema_rule(ev[j], (float)(bf16_t)pv[j], keep, take);  // the value the store below rounds to
+    }
+    if constexpr (MASTER) Vec8<float>::store(master + i * 8, pv);
+    Vec8<bf16_t>::store(p + i * 8, pv);
+    Vec8<float>::store(m + i * 8, mv);
+    Vec8<float>::store(v + i * 8, vv);
+    Vec8<float>::store(e + i * 8, ev);
+  }
+}
+
 // sum of squares, stage 1: one partial per workgroup (grid-stride over 8-element vectors); stage 2 folds the partials
 __global__ __launch_bounds__(256) void sqnorm_partial_kernel(const bf16_t* __restrict__ x, int64_t n8, float* __restrict__ part) {
   __shared__ float red[4];
@@ -1116,6 +1204,43 @@ int op_adamw_step_groups_master(void* p, float* master, const void* g, float* m,
   hipLaunchKernelGGL(adamw_groups_master_kernel, dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p, master,
                      (const bf16_t*)g, m, v, numel / 8, group_end8, group_lr_scale, group_weight_decay, (int)n_groups, lr, beta1,
                      beta2, eps, (float)(sqrt(bc2) / bc1), grad_scale, grad_sqnorm, clip_norm);
+  OP_LAUNCH_CHECK();
+  return OP_OK;
+}
+
+// One EMA update of a flat fp32 shadow from the flat bf16 parameters (include/onepeace_hip.h): 10 B/param.
+int op_ema_step(float* ema, const void* p, int64_t numel, float keep, float take, void* stream) {
+  OP_CHECK_ARG(ema && p, "ema_step: null pointer");
+  OP_CHECK_ARG(numel % 8 == 0, "ema_step: numel must be a multiple of 8");
+  if (numel == 0) return OP_OK;
+  hipLaunchKernelGGL(ema_step_kernel, dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, ema, (const bf16_t*)p, numel / 8,
+                     keep, take);
+  OP_LAUNCH_CHECK();
+  return OP_OK;
+}
+
+// op_adamw_step_groups (master == NULL) or op_adamw_step_groups_master followed by op_ema_step on the new p, in ONE launch:
+// 30 / 36 B/param instead of 22 + 10 / 28 + 10.  Same tables, clip handling and argument checks; ema != NULL and apart from master.
+int op_adamw_step_groups_ema(void* p, float* master, const void* g, float* m, float* v, float* ema, int64_t numel,
+                             const int64_t* group_end8, const float* group_lr_scale, const float* group_weight_decay,
+                             int64_t n_groups, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
+                             const float* grad_sqnorm, float clip_norm, float ema_keep, float ema_take, void* stream) {
+  OP_CHECK_ARG(p && g && m && v && ema && group_end8 && group_lr_scale && group_weight_decay, "adamw_groups_ema: null pointer");
+  OP_CHECK_ARG(numel % 8 == 0 && step >= 1 && n_groups >= 1 && n_groups <= ADAM_MAX_GROUPS,
+               "adamw_groups_ema: numel %% 8 == 0, step >= 1, 1 <= n_groups <= %d required", ADAM_MAX_GROUPS);
+  OP_CHECK_ARG(master == nullptr || (ema + numel <= master || master + numel <= ema), "adamw_groups_ema: ema overlaps master");
+  if (numel == 0) return OP_OK;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const float bias_corr = (float)(sqrt(bc2) / bc1);
+  if (master)
+    hipLaunchKernelGGL(adamw_groups_ema_kernel<true>, dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p, master,
+                       (const bf16_t*)g, m, v, ema, numel / 8, group_end8, group_lr_scale, group_weight_decay, (int)n_groups, lr,
+                       beta1, beta2, eps, bias_corr, grad_scale, grad_sqnorm, clip_norm, ema_keep, ema_take);
+  else
+    hipLaunchKernelGGL(adamw_groups_ema_kernel<false>, dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p,
+                       (float*)nullptr, (const bf16_t*)g, m, v, ema, numel / 8, group_end8, group_lr_scale, group_weight_decay,
+                       (int)n_groups, lr, beta1, beta2, eps, bias_corr, grad_scale, grad_sqnorm, clip_norm, ema_keep, ema_take);
   OP_LAUNCH_CHECK();
   return OP_OK;
 }

@@ -69,6 +69,9 @@ SIGNATURES = {
     "op_adamw_step_groups": (c_int, [P, P, P, P, I64, P, P, P, I64, c_float, c_float, c_float, c_float, I64, c_float, P, c_float, P]),
     "op_adamw_step_groups_master": (c_int, [P, P, P, P, P, I64, P, P, P, I64, c_float, c_float, c_float, c_float, I64, c_float, P,
                                            c_float, P]),
+    "op_ema_step": (c_int, [P, P, I64, c_float, c_float, P]),
+    "op_adamw_step_groups_ema": (c_int, [P, P, P, P, P, P, I64, P, P, P, I64, c_float, c_float, c_float, c_float, I64, c_float, P,
+                                        c_float, c_float, c_float, P]),
     "op_sqnorm": (c_int, [P, I64, P, P, P]),
     "op_relpos_bias_build": (c_int, [P, P, I64, P, I64, I64, I64, c_int, P]),
     "op_relpos_bias_bwd": (c_int, [P, I64, I64, P, P, I64, P, I64, P, P, I64, P]),
@@ -810,6 +813,34 @@ def adamw_step_groups_master(p, master, g, m, v, group_end8, group_lr_scale, gro
     _check(lib().op_adamw_step_groups_master(ptr(p), ptr(master), ptr(g), ptr(m), ptr(v), p.numel(), ptr(group_end8),
                                              ptr(group_lr_scale), ptr(group_wd), group_end8.numel(), lr, beta1, beta2, eps, step,
                                              grad_scale, ptr(grad_sqnorm), clip_norm, stream()), "op_adamw_step_groups_master")
+
+
+def _req_ema(t, p, name="ema"):
+    """The kernels run over p.numel() elements of `t`: a shorter, strided or non-fp32 buffer would be read and written out of bounds."""
+    if t is None:
+        return  # the C entry refuses a null average
+    _req(t, name, torch.float32)
+    _req(p, "p", torch.bfloat16)
+    if t.numel() != p.numel():
+        raise RuntimeError("%s has %d elements, p has %d" % (name, t.numel(), p.numel()))
+
+
+def ema_step(ema, p, keep, take):
+    """ema (fp32) <- fmaf(take, float(p), keep * ema) over the flat bf16 `p`: one step of the fp32 weight average (ema.FlatEMA)."""
+    _req_ema(ema, p)
+    _check(lib().op_ema_step(ptr(ema), ptr(p), p.numel(), keep, take, stream()), "op_ema_step")
+
+
+def adamw_step_groups_ema(p, master, g, m, v, ema, group_end8, group_lr_scale, group_wd, lr, beta1, beta2, eps, step, ema_keep,
+                          ema_take, grad_scale=1.0, grad_sqnorm=None, clip_norm=0.0):
+    """adamw_step_groups (master None) or adamw_step_groups_master, and ema_step on the parameters it stores, in one launch."""
+    _req_ema(ema, p)
+    if master is not None:
+        _req_ema(master, p, "master")
+    _check(lib().op_adamw_step_groups_ema(ptr(p), ptr(master), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), ptr(group_end8),
+                                          ptr(group_lr_scale), ptr(group_wd), group_end8.numel(), lr, beta1, beta2, eps, step,
+                                          grad_scale, ptr(grad_sqnorm), clip_norm, ema_keep, ema_take, stream()),
+           "op_adamw_step_groups_ema")
 
 
 def sqnorm(x, out=None):

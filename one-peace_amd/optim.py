@@ -16,6 +16,9 @@ Two arrangements of the bf16 parameters, as the reference has them (trainer.py:2
     what Adam updates, and the bf16 parameters are its cast after every step.  28 bytes/parameter of traffic and +4 bytes/parameter
     of memory: +15.6 GB at the 4B model, against 267 of 309 GB reserved at the headline batch.
 
+Both optimisers take ``ema=``, an ``ema.FlatEMA`` over the same flat buffers: the reference trainer's fp32 weight average
+(trainer.py:243-250, :895-907), updated from the new bf16 parameters inside the same launch (+8 bytes/parameter).
+
 Deviation from the reference, stated, for the memory-efficient arrangement only: global-norm clipping multiplies the gradient by
 the clip coefficient in fp32 inside the update kernel; the reference scales its bf16 gradients in place first
 (fairseq/utils.py:393-397: one extra bf16 rounding).  With master weights the reference itself multiplies fp32 gradients
@@ -58,17 +61,26 @@ def reference_param_groups(model, num_layers=None, layer_decay=1.0):
     return no_decay, lr_scale
 
 
+def _checked_ema(ema, flat):
+    if ema is not None and ema.flat is not flat:
+        raise ValueError("the FlatEMA was built over other FlatParameters than this optimiser")
+    return ema
+
+
 class FusedAdamW:
     """master_weights=True keeps ``self.master``, an fp32 copy of ``flat.params`` taken at construction: the step updates the master
     and writes ``flat.params`` as its bf16 cast, without reading it.  Anything written into ``flat.params`` from outside afterwards
     (weights loaded into the model once the optimiser exists) must be followed by ``sync_master()``: otherwise the next step
-    overwrites it with the cast of the old master."""
+    overwrites it with the cast of the old master.
+    ema: an ``ema.FlatEMA`` over the same ``flat``.  The step then updates the fp32 weight average from the new bf16 parameters in the
+    same launch (with or without the master) and advances ``ema.num_updates``; nothing else has to call ``ema.step()``."""
 
-    def __init__(self, flat: FlatParameters, lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.05, master_weights=False):
+    def __init__(self, flat: FlatParameters, lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.05, master_weights=False, ema=None):
         if not flat.params.is_cuda or flat.params.dtype != torch.bfloat16:
             raise RuntimeError("FusedAdamW needs bf16 parameters on an MI355X (the HIP path has no CPU fallback)")
         self.flat = flat
         self.master = flat.params.float() if master_weights else None
+        self.ema = _checked_ema(ema, flat)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros(flat.numel, dtype=torch.float32, device=flat.params.device)
         self.exp_avg_sq = torch.zeros_like(self.exp_avg)
@@ -102,7 +114,13 @@ class FusedAdamW:
         self.step_count += 1
         f = self.flat
         sq = hip.sqnorm(f.grads) if clip_norm > 0 else None
-        if self.master is None:
+        if self.ema is not None:  # the average of the new bf16 parameters, in the same launch (ema.py)
+            keep, take = self.ema.coefficients(self.ema.num_updates + 1)
+            hip.adamw_step_groups_ema(f.params, self.master, f.grads, self.exp_avg, self.exp_avg_sq, self.ema.shadow, self._end8,
+                                      self._scale, self._wd, self.lr, self.betas[0], self.betas[1], self.eps, self.step_count, keep,
+                                      take, grad_scale, sq, clip_norm)
+            self.ema.num_updates += 1
+        elif self.master is None:
             hip.adamw_step_groups(f.params, f.grads, self.exp_avg, self.exp_avg_sq, self._end8, self._scale, self._wd, self.lr,
                                   self.betas[0], self.betas[1], self.eps, self.step_count, grad_scale, sq, clip_norm)
         else:
@@ -120,11 +138,13 @@ class TorchAdamW:
     """The same update over ``FlatParameters`` written with torch ops (fp32 math on the flat buffers, any device / dtype): the
     optimiser of the CPU control-flow runs of the data-parallel step (``bench.py --debug-cpu-micro``, world-size-4 gloo test) and
     a readable statement of what the fused kernel computes.  Same interface as ``FusedAdamW``, ``master_weights`` included: with
-    it the fp32 ``self.master`` is what the rule reads and writes, and ``flat.params`` receives its cast."""
+    it the fp32 ``self.master`` is what the rule reads and writes, and ``flat.params`` receives its cast.  With ``ema`` the step ends
+    with ``ema.step()``."""
 
-    def __init__(self, flat: FlatParameters, lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.05, master_weights=False):
+    def __init__(self, flat: FlatParameters, lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.05, master_weights=False, ema=None):
         self.flat = flat
         self.master = flat.params.float() if master_weights else None
+        self.ema = _checked_ema(ema, flat)
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros(flat.numel, dtype=torch.float32, device=flat.params.device)
         self.exp_avg_sq = torch.zeros_like(self.exp_avg)
@@ -165,6 +185,8 @@ class TorchAdamW:
                 self.master[start:end].copy_(new)
                 new = self.master[start:end].to(f.params.dtype)
             f.params[start:end].copy_(new)
+        if self.ema is not None:
+            self.ema.step()
         if f.params.is_cuda:
             ops.refresh_weight_cache()
         return norm
