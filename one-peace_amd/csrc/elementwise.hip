@@ -435,164 +435,6 @@ __global__ __launch_bounds__(256) void infonce_rows_kernel(float* __restrict__ s
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// AdamW as the reference does it (one_peace/optim/adam.py:186-253): fp32 math on bf16 params, decoupled
-// decay applied to the parameter before the Adam update, eps added to sqrt(v).
-// Algorithmic bytes: 22 B/param (p r+w 4, g r 2, m and v r+w 16).
-// Non-finite gradients with clipping on: a NaN anywhere in the gradient buffer makes the norm NaN, the clip coefficient NaN
-// (fminf would have returned 1 and stepped every other parameter with the unclipped gradient) and with it EVERY parameter and
-// moment of the step, as optim.TorchAdamW's clamp does; an infinite norm gives coefficient 0, and only the infinite elements
-// turn NaN.  The reference raises before its optimiser step instead (trainer.py:830-837): the norm is what a loop checks.
-// ------------------------------------------------------------------------------------------------------------
-// grad_scale times the reference's clip coefficient (fairseq/utils.py:393-397: clamp(max_norm / (norm + 1e-6), max=1), norm =
-// |grad_scale| sqrt(sqnorm)).  torch's clamp, not fminf: a NaN coefficient stays NaN.  Formed in fp64 and rounded ONCE: every
-// gradient is multiplied by this number and v by its square, so the four fp32 roundings of sqrtf, the sum, the quotient and the
-// product reached v doubled (measured: 1.19 x the bound tests/adamw_ref.py derives for v).  A handful of fp64 operations per thread.
-__device__ __forceinline__ float clipped_grad_scale(float grad_scale, const float* __restrict__ sqnorm, float clip_norm) {
-  if (sqnorm == nullptr || !(clip_norm > 0.f)) return grad_scale;
-  const double norm = fabs((double)grad_scale) * sqrt((double)*sqnorm);
-  const double c = (double)clip_norm / (norm + 1e-6);
-  return (c < 1.0 || c != c) ? (float)((double)grad_scale * c) : grad_scale;
-}
-
-__global__ __launch_bounds__(256) void adamw_kernel(bf16_t* __restrict__ p, const bf16_t* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v, int64_t n8,
-                                                    float beta1, float beta2, float eps, float step_size,
-                                                    float decay_mul, float grad_scale, const float* __restrict__ sqnorm,
-                                                    float clip_norm) {
-  grad_scale = clipped_grad_scale(grad_scale, sqnorm, clip_norm);
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
-    float pv[8], gv[8], mv[8], vv[8];
-    Vec8<bf16_t>::load(p + i * 8, pv);
-    Vec8<bf16_t>::load(g + i * 8, gv);
-    Vec8<float>::load(m + i * 8, mv);
-    Vec8<float>::load(v + i * 8, vv);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gr = gv[j] * grad_scale;
-      mv[j] = mv[j] * beta1 + (1.f - beta1) * gr;
-      vv[j] = vv[j] * beta2 + (1.f - beta2) * gr * gr;
-      const float denom = sqrtf(vv[j]) + eps;
-      pv[j] = pv[j] * decay_mul - step_size * (mv[j] / denom);
-    }
-    Vec8<bf16_t>::store(p + i * 8, pv);
-    Vec8<float>::store(m + i * 8, mv);
-    Vec8<float>::store(v + i * 8, vv);
-  }
-}
-
-// The same update over a flat buffer that is partitioned into parameter groups (trainer.py:265-278, utils/layer_decay.py:34-77:
-// "layer_<id>_<decay|no_decay>" groups with their own lr_scale and weight decay; optim/base_optimizer.py:8-14 sets
-// lr_g = lr * lr_scale_g): group g owns the 8-element vectors [end8[g-1], end8[g]).  ONE launch for all groups: the group of a
-// vector is found by binary search in a table staged in LDS (<= 256 groups), and re-used while consecutive vectors stay in it.
-constexpr int ADAM_MAX_GROUPS = 256;
-__global__ __launch_bounds__(256) void adamw_groups_kernel(bf16_t* __restrict__ p, const bf16_t* __restrict__ g,
-                                                           float* __restrict__ m, float* __restrict__ v, int64_t n8,
-                                                           const int64_t* __restrict__ end8, const float* __restrict__ lr_scale,
-                                                           const float* __restrict__ wd, int n_groups, float lr, float beta1,
-                                                           float beta2, float eps, float bias_corr, float grad_scale,
-                                                           const float* __restrict__ sqnorm, float clip_norm) {
-  __shared__ int64_t s_end[ADAM_MAX_GROUPS];
-  __shared__ float s_step[ADAM_MAX_GROUPS], s_decay[ADAM_MAX_GROUPS];
-  for (int i = threadIdx.x; i < n_groups; i += 256) {
-    const float lr_g = lr * lr_scale[i];
-    s_end[i] = end8[i];
-    s_step[i] = lr_g * bias_corr;          // lr_g * sqrt(1 - beta2^t) / (1 - beta1^t)
-    s_decay[i] = 1.f - wd[i] * lr_g;       // p <- p - wd * lr_g * p, before the Adam update (adam.py:243-246)
-  }
-  __syncthreads();
-  grad_scale = clipped_grad_scale(grad_scale, sqnorm, clip_norm);
-  int grp = 0;
-  int64_t lo = 0, hi = s_end[0];
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
-    if (i < lo || i >= hi) {  // first group whose end is > i
-      int a = 0, b = n_groups - 1;
-      while (a < b) {
-        const int mid = (a + b) >> 1;
-        if (s_end[mid] > i) b = mid; else a = mid + 1;
-      }
-      grp = a;
-      lo = grp ? s_end[grp - 1] : 0;
-      hi = s_end[grp];
-    }
-    const float step_size = s_step[grp], decay_mul = s_decay[grp];
-    float pv[8], gv[8], mv[8], vv[8];
-    Vec8<bf16_t>::load(p + i * 8, pv);
-    Vec8<bf16_t>::load(g + i * 8, gv);
-    Vec8<float>::load(m + i * 8, mv);
-    Vec8<float>::load(v + i * 8, vv);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gr = gv[j] * grad_scale;
-      mv[j] = mv[j] * beta1 + (1.f - beta1) * gr;
-      vv[j] = vv[j] * beta2 + (1.f - beta2) * gr * gr;
-      const float denom = sqrtf(vv[j]) + eps;
-      pv[j] = pv[j] * decay_mul - step_size * (mv[j] / denom);
-    }
-    Vec8<bf16_t>::store(p + i * 8, pv);
-    Vec8<float>::store(m + i * 8, mv);
-    Vec8<float>::store(v + i * 8, vv);
-  }
-}
-
-// The same update with an fp32 master copy of the parameters (the reference's `bf16: true` without `memory_efficient_bf16`:
-// trainer.py:297-307 -> optim/fp16_optimizer.py: Adam runs on fp32_params, _sync_fp32_params_to_fp16 casts them back).  The
-// master takes the place of float(p): it is read, updated with the expressions of adamw_groups_kernel and stored in fp32, and p
-// receives the round-to-nearest-even bf16 of the value just stored.  p is never read, so an update below half a bf16 spacing
-// accumulates in the master instead of being rounded away every step.
-// Algorithmic bytes: 28 B/param (master r+w 8, g r 2, m and v r+w 16, p w 2).  Group lookup and non-finite behaviour as above.
-__global__ __launch_bounds__(256) void adamw_groups_master_kernel(bf16_t* __restrict__ p, float* __restrict__ master,
-                                                                  const bf16_t* __restrict__ g, float* __restrict__ m,
-                                                                  float* __restrict__ v, int64_t n8,
-                                                                  const int64_t* __restrict__ end8,
-                                                                  const float* __restrict__ lr_scale, const float* __restrict__ wd,
-                                                                  int n_groups, float lr, float beta1, float beta2, float eps,
-                                                                  float bias_corr, float grad_scale,
-                                                                  const float* __restrict__ sqnorm, float clip_norm) {
-  __shared__ int64_t s_end[ADAM_MAX_GROUPS];
-  __shared__ float s_step[ADAM_MAX_GROUPS], s_decay[ADAM_MAX_GROUPS];
-  for (int i = threadIdx.x; i < n_groups; i += 256) {
-    const float lr_g = lr * lr_scale[i];
-    s_end[i] = end8[i];
-    s_step[i] = lr_g * bias_corr;
-    s_decay[i] = 1.f - wd[i] * lr_g;
-  }
-  __syncthreads();
-  grad_scale = clipped_grad_scale(grad_scale, sqnorm, clip_norm);
-  int grp = 0;
-  int64_t lo = 0, hi = s_end[0];
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
-    if (i < lo || i >= hi) {  // first group whose end is > i
-      int a = 0, b = n_groups - 1;
-      while (a < b) {
-        const int mid = (a + b) >> 1;
-        if (s_end[mid] > i) b = mid; else a = mid + 1;
-      }
-      grp = a;
-      lo = grp ? s_end[grp - 1] : 0;
-      hi = s_end[grp];
-    }
-    const float step_size = s_step[grp], decay_mul = s_decay[grp];
-    float pv[8], gv[8], mv[8], vv[8];
-    Vec8<float>::load(master + i * 8, pv);
-    Vec8<bf16_t>::load(g + i * 8, gv);
-    Vec8<float>::load(m + i * 8, mv);
-    Vec8<float>::load(v + i * 8, vv);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gr = gv[j] * grad_scale;
-      mv[j] = mv[j] * beta1 + (1.f - beta1) * gr;
-      vv[j] = vv[j] * beta2 + (1.f - beta2) * gr * gr;
-      const float denom = sqrtf(vv[j]) + eps;
-      pv[j] = pv[j] * decay_mul - step_size * (mv[j] / denom);
-    }
-    Vec8<float>::store(master + i * 8, pv);
-    Vec8<bf16_t>::store(p + i * 8, pv);  // bf16(master'), round to nearest even: the reference's _sync_fp32_params_to_fp16
-    Vec8<float>::store(m + i * 8, mv);
-    Vec8<float>::store(v + i * 8, vv);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------
 // Exponential moving average of the weights in fp32 (the reference's EMAModule with ema_fp32: true; the rule is the one of
 // fairseq/modules/ema_module.py:101-127: ema.mul_(decay); ema.add_(param.to(ema.dtype), alpha=1 - decay)):
 //   e' = fmaf(take, p, fl32(keep * e))       keep = float(decay), take = float(1 - decay), p the bf16 parameter as stored
@@ -617,52 +459,86 @@ __global__ __launch_bounds__(256) void ema_step_kernel(float* __restrict__ e, co
   }
 }
 
-// adamw_groups_kernel (MASTER = false) / adamw_groups_master_kernel (MASTER = true) with the EMA pass folded in: the same
-// expressions in the same order for p, master, m and v, one more fp32 stream e, and after the update the rule above with the value
-// the bf16 store of p rounds to -- also with a master: the reference's EMA reads the model, never the optimiser's fp32 copy.
-// Algorithmic bytes: 30 B/param without the master (22 + e r+w 8), 36 B/param with it (28 + 8).  Group lookup and non-finite
-// behaviour as above; a NaN clip coefficient makes every parameter NaN and with it every element of e.
-template <bool MASTER>
-__global__ __launch_bounds__(256) void adamw_groups_ema_kernel(bf16_t* __restrict__ p, float* __restrict__ master,
-                                                               const bf16_t* __restrict__ g, float* __restrict__ m,
-                                                               float* __restrict__ v, float* __restrict__ e, int64_t n8,
-                                                               const int64_t* __restrict__ end8,
-                                                               const float* __restrict__ lr_scale, const float* __restrict__ wd,
-                                                               int n_groups, float lr, float beta1, float beta2, float eps,
-                                                               float bias_corr, float grad_scale,
-                                                               const float* __restrict__ sqnorm, float clip_norm, float keep,
-                                                               float take) {
-  __shared__ int64_t s_end[ADAM_MAX_GROUPS];
+// ------------------------------------------------------------------------------------------------------------
+// AdamW as the reference does it (one_peace/optim/adam.py:186-253): fp32 math on bf16 params, decoupled decay applied to the
+// parameter before the Adam update, eps added to sqrt(v).  ONE kernel template states the update; three switches select what is read
+// and written around it, so p, master, m and v cannot depend on them.  What a switch leaves unused arrives as null or 0, never read.
+//   GROUPS  the flat buffer is partitioned into parameter groups (trainer.py:265-278, utils/layer_decay.py:34-77:
+//           "layer_<id>_<decay|no_decay>" groups with their own lr_scale and weight decay; optim/base_optimizer.py:8-14 sets
+//           lr_g = lr * lr_scale_g): group g owns the 8-element vectors [end8[g-1], end8[g]).  ONE launch for all groups: the group
+//           of a vector is found by binary search in a table staged in LDS (<= 256 groups), and re-used while consecutive vectors
+//           stay in it; step_size and decay_mul are formed per group in fp32 on the device.  Without GROUPS both arrive as scalars
+//           that the host formed (op_adamw_step), and there is no table and no search.
+//   MASTER  an fp32 master copy of the parameters (the reference's `bf16: true` without `memory_efficient_bf16`:
+//           trainer.py:297-307 -> optim/fp16_optimizer.py: Adam runs on fp32_params, _sync_fp32_params_to_fp16 casts them back).
+//           The master takes the place of float(p): it is read, updated and stored in fp32, and p receives the round-to-nearest-even
+//           bf16 of the value just stored.  p is never read, so an update below half a bf16 spacing accumulates in the master
+//           instead of being rounded away every step.
+//   EMA     the EMA pass folded in: one more fp32 stream e, and after the update ema_rule with the value the bf16 store of p
+//           rounds to -- also with a master: the reference's EMA reads the model, never the optimiser's fp32 copy.
+// Algorithmic bytes per parameter: 22 plain or with GROUPS alone (p r+w 4, g r 2, m and v r+w 16); 28 with MASTER (master r+w 8,
+// g r 2, m and v r+w 16, p w 2); with EMA 30 without the master (22 + e r+w 8) and 36 with it (28 + 8).
+// Non-finite gradients with clipping on: a NaN anywhere in the gradient buffer makes the norm NaN, the clip coefficient NaN
+// (fminf would have returned 1 and stepped every other parameter with the unclipped gradient) and with it EVERY parameter and
+// moment of the step, as optim.TorchAdamW's clamp does, and with every parameter every element of e; an infinite norm gives
+// coefficient 0, and only the infinite elements turn NaN.  The reference raises before its optimiser step instead
+// (trainer.py:830-837): the norm is what a loop checks.
+// ------------------------------------------------------------------------------------------------------------
+// grad_scale times the reference's clip coefficient (fairseq/utils.py:393-397: clamp(max_norm / (norm + 1e-6), max=1), norm =
+// |grad_scale| sqrt(sqnorm)).  torch's clamp, not fminf: a NaN coefficient stays NaN.  Formed in fp64 and rounded ONCE: every
+// gradient is multiplied by this number and v by its square, so the four fp32 roundings of sqrtf, the sum, the quotient and the
+// product reached v doubled (measured: 1.19 x the bound tests/adamw_ref.py derives for v).  A handful of fp64 operations per thread.
+__device__ __forceinline__ float clipped_grad_scale(float grad_scale, const float* __restrict__ sqnorm, float clip_norm) {
+  if (sqnorm == nullptr || !(clip_norm > 0.f)) return grad_scale;
+  const double norm = fabs((double)grad_scale) * sqrt((double)*sqnorm);
+  const double c = (double)clip_norm / (norm + 1e-6);
+  return (c < 1.0 || c != c) ? (float)((double)grad_scale * c) : grad_scale;
+}
+
+constexpr int ADAM_MAX_GROUPS = 256;
+template <bool GROUPS, bool MASTER, bool EMA>
+__global__ __launch_bounds__(256) void adamw_kernel(bf16_t* __restrict__ p, float* __restrict__ master,
+                                                    const bf16_t* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                    float* __restrict__ e, int64_t n8, const int64_t* __restrict__ end8,
+                                                    const float* __restrict__ lr_scale, const float* __restrict__ wd,
+                                                    int n_groups, float lr, float bias_corr, float step_size, float decay_mul,
+                                                    float beta1, float beta2, float eps, float grad_scale,
+                                                    const float* __restrict__ sqnorm, float clip_norm, float keep, float take) {
+  __shared__ int64_t s_end[ADAM_MAX_GROUPS];  // unused, and not allocated, without GROUPS
   __shared__ float s_step[ADAM_MAX_GROUPS], s_decay[ADAM_MAX_GROUPS];
-  for (int i = threadIdx.x; i < n_groups; i += 256) {
-    const float lr_g = lr * lr_scale[i];
-    s_end[i] = end8[i];
-    s_step[i] = lr_g * bias_corr;
-    s_decay[i] = 1.f - wd[i] * lr_g;
+  if constexpr (GROUPS) {
+    for (int i = threadIdx.x; i < n_groups; i += 256) {
+      const float lr_g = lr * lr_scale[i];
+      s_end[i] = end8[i];
+      s_step[i] = lr_g * bias_corr;          // lr_g * sqrt(1 - beta2^t) / (1 - beta1^t)
+      s_decay[i] = 1.f - wd[i] * lr_g;       // p <- p - wd * lr_g * p, before the Adam update (adam.py:243-246)
+    }
+    __syncthreads();
   }
-  __syncthreads();
   grad_scale = clipped_grad_scale(grad_scale, sqnorm, clip_norm);
   int grp = 0;
-  int64_t lo = 0, hi = s_end[0];
+  int64_t lo = 0, hi = GROUPS ? s_end[0] : 0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
-    if (i < lo || i >= hi) {  // first group whose end is > i
-      int a = 0, b = n_groups - 1;
-      while (a < b) {
-        const int mid = (a + b) >> 1;
-        if (s_end[mid] > i) b = mid; else a = mid + 1;
+    if constexpr (GROUPS) {
+      if (i < lo || i >= hi) {  // first group whose end is > i
+        int a = 0, b = n_groups - 1;
+        while (a < b) {
+          const int mid = (a + b) >> 1;
+          if (s_end[mid] > i) b = mid; else a = mid + 1;
+        }
+        grp = a;
+        lo = grp ? s_end[grp - 1] : 0;
+        hi = s_end[grp];
       }
-      grp = a;
-      lo = grp ? s_end[grp - 1] : 0;
-      hi = s_end[grp];
+      step_size = s_step[grp], decay_mul = s_decay[grp];
     }
-    const float step_size = s_step[grp], decay_mul = s_decay[grp];
     float pv[8], gv[8], mv[8], vv[8], ev[8];
     if constexpr (MASTER) Vec8<float>::load(master + i * 8, pv);
     else Vec8<bf16_t>::load(p + i * 8, pv);
     Vec8<bf16_t>::load(g + i * 8, gv);
     Vec8<float>::load(m + i * 8, mv);
     Vec8<float>::load(v + i * 8, vv);
-    Vec8<float>::load(e + i * 8, ev);
+    if constexpr (EMA) Vec8<float>::load(e + i * 8, ev);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float gr = gv[j] * grad_scale;
@@ -670,13 +546,13 @@ __global__ __launch_bounds__(256) void adamw_groups_ema_kernel(bf16_t* __restric
       vv[j] = vv[j] * beta2 + (1.f - beta2) * gr * gr;
       const float denom = sqrtf(vv[j]) + eps;
       pv[j] = pv[j] * decay_mul - step_size * (mv[j] / denom);
-      ev[j] = ema_rule(ev[j], (float)(bf16_t)pv[j], keep, take);  // the value the store below rounds to
+      if constexpr (EMA) ev[j] = ema_rule(ev[j], (float)(bf16_t)pv[j], keep, take);  // the value the store below rounds to
     }
     if constexpr (MASTER) Vec8<float>::store(master + i * 8, pv);
-    Vec8<bf16_t>::store(p + i * 8, pv);
+    Vec8<bf16_t>::store(p + i * 8, pv);  // with MASTER: bf16(master'), round to nearest even: the reference's _sync_fp32_params_to_fp16
     Vec8<float>::store(m + i * 8, mv);
     Vec8<float>::store(v + i * 8, vv);
-    Vec8<float>::store(e + i * 8, ev);
+    if constexpr (EMA) Vec8<float>::store(e + i * 8, ev);
   }
 }
 
@@ -1148,6 +1024,34 @@ int op_sqnorm(const void* x, int64_t numel, float* workspace, float* out, void* 
   return OP_OK;
 }
 
+// What the four op_adamw_step* entries share: the argument checks (messages carry the entry's prefix `who`), the bias correction
+// and the launch of adamw_kernel<groups, master != NULL, ema != NULL>.  An entry that requires master or ema checks that itself.
+// Without groups step_size and decay_mul are formed here, step_size in fp64 and rounded once; with groups the device forms them.
+static int adamw_launch(const char* who, bool groups, void* p, float* master, const void* g, float* m, float* v, float* ema,
+                        int64_t numel, const int64_t* group_end8, const float* group_lr_scale, const float* group_weight_decay,
+                        int64_t n_groups, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
+                        float grad_scale, const float* grad_sqnorm, float clip_norm, float ema_keep, float ema_take, void* stream) {
+  OP_CHECK_ARG(p && g && m && v && (!groups || (group_end8 && group_lr_scale && group_weight_decay)), "%s: null pointer", who);
+  OP_CHECK_ARG(numel % 8 == 0 && step >= 1 && (!groups || (n_groups >= 1 && n_groups <= ADAM_MAX_GROUPS)),
+               groups ? "%s: numel %% 8 == 0, step >= 1, 1 <= n_groups <= %d required" : "%s: numel must be a multiple of 8 and step >= 1",
+               who, ADAM_MAX_GROUPS);
+  OP_CHECK_ARG(!master || !ema || ema + numel <= master || master + numel <= ema, "%s: ema overlaps master", who);
+  if (numel == 0) return OP_OK;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const float bias_corr = groups ? (float)(sqrt(bc2) / bc1) : 0.f;
+  const float step_size = groups ? 0.f : (float)((double)lr * sqrt(bc2) / bc1);
+  const float decay_mul = groups ? 0.f : 1.f - weight_decay * lr;
+  static constexpr decltype(&adamw_kernel<true, false, false>) with_groups[] = {  // [master + 2 ema]; with the plain kernel: all five
+      adamw_kernel<true, false, false>, adamw_kernel<true, true, false>, adamw_kernel<true, false, true>, adamw_kernel<true, true, true>};
+  hipLaunchKernelGGL((groups ? with_groups[(master != nullptr) + 2 * (ema != nullptr)] : adamw_kernel<false, false, false>),
+                     dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p, master, (const bf16_t*)g, m, v, ema,
+                     numel / 8, group_end8, group_lr_scale, group_weight_decay, (int)n_groups, lr, bias_corr, step_size, decay_mul,
+                     beta1, beta2, eps, grad_scale, grad_sqnorm, clip_norm, ema_keep, ema_take);
+  OP_LAUNCH_CHECK();
+  return OP_OK;
+}
+
 // One AdamW update over a flat bf16 parameter range (numel % 8 == 0).  step >= 1.  The gradient is multiplied by
 // grad_scale (1/world after a SUM all-reduce, trainer.py:917-923) and, when grad_sqnorm (device scalar = sum of squares of
 // the UNSCALED gradients of ALL ranges, op_sqnorm) and clip_norm > 0 are given, by the reference's clip coefficient
@@ -1155,17 +1059,8 @@ int op_sqnorm(const void* x, int64_t numel, float* workspace, float* out, void* 
 int op_adamw_step(void* p, const void* g, float* m, float* v, int64_t numel, float lr, float beta1, float beta2, float eps,
                   float weight_decay, int64_t step, float grad_scale, const float* grad_sqnorm, float clip_norm,
                   void* stream) {
-  OP_CHECK_ARG(p && g && m && v, "adamw: null pointer");
-  OP_CHECK_ARG(numel % 8 == 0 && step >= 1, "adamw: numel must be a multiple of 8 and step >= 1");
-  if (numel == 0) return OP_OK;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr * sqrt(bc2) / bc1);
-  const float decay_mul = 1.f - weight_decay * lr;
-  hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p, (const bf16_t*)g,
-                     m, v, numel / 8, beta1, beta2, eps, step_size, decay_mul, grad_scale, grad_sqnorm, clip_norm);
-  OP_LAUNCH_CHECK();
-  return OP_OK;
+  return adamw_launch("adamw", false, p, nullptr, g, m, v, nullptr, numel, nullptr, nullptr, nullptr, 0, lr, beta1, beta2, eps,
+                      weight_decay, step, grad_scale, grad_sqnorm, clip_norm, 0.f, 0.f, stream);
 }
 
 // AdamW over a flat buffer partitioned into n_groups (<= 256) contiguous parameter groups in ONE launch: group g covers
@@ -1176,17 +1071,8 @@ int op_adamw_step_groups(void* p, const void* g, float* m, float* v, int64_t num
                          const float* group_lr_scale, const float* group_weight_decay, int64_t n_groups, float lr, float beta1,
                          float beta2, float eps, int64_t step, float grad_scale, const float* grad_sqnorm, float clip_norm,
                          void* stream) {
-  OP_CHECK_ARG(p && g && m && v && group_end8 && group_lr_scale && group_weight_decay, "adamw_groups: null pointer");
-  OP_CHECK_ARG(numel % 8 == 0 && step >= 1 && n_groups >= 1 && n_groups <= ADAM_MAX_GROUPS,
-               "adamw_groups: numel %% 8 == 0, step >= 1, 1 <= n_groups <= %d required", ADAM_MAX_GROUPS);
-  if (numel == 0) return OP_OK;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  hipLaunchKernelGGL(adamw_groups_kernel, dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p,
-                     (const bf16_t*)g, m, v, numel / 8, group_end8, group_lr_scale, group_weight_decay, (int)n_groups, lr, beta1,
-                     beta2, eps, (float)(sqrt(bc2) / bc1), grad_scale, grad_sqnorm, clip_norm);
-  OP_LAUNCH_CHECK();
-  return OP_OK;
+  return adamw_launch("adamw_groups", true, p, nullptr, g, m, v, nullptr, numel, group_end8, group_lr_scale, group_weight_decay,
+                      n_groups, lr, beta1, beta2, eps, 0.f, step, grad_scale, grad_sqnorm, clip_norm, 0.f, 0.f, stream);
 }
 
 // op_adamw_step_groups with an fp32 master copy (include/onepeace_hip.h): master is read and written, p only written
@@ -1195,17 +1081,10 @@ int op_adamw_step_groups_master(void* p, float* master, const void* g, float* m,
                                 const int64_t* group_end8, const float* group_lr_scale, const float* group_weight_decay,
                                 int64_t n_groups, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
                                 const float* grad_sqnorm, float clip_norm, void* stream) {
-  OP_CHECK_ARG(p && master && g && m && v && group_end8 && group_lr_scale && group_weight_decay, "adamw_groups_master: null pointer");
-  OP_CHECK_ARG(numel % 8 == 0 && step >= 1 && n_groups >= 1 && n_groups <= ADAM_MAX_GROUPS,
-               "adamw_groups_master: numel %% 8 == 0, step >= 1, 1 <= n_groups <= %d required", ADAM_MAX_GROUPS);
-  if (numel == 0) return OP_OK;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  hipLaunchKernelGGL(adamw_groups_master_kernel, dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p, master,
-                     (const bf16_t*)g, m, v, numel / 8, group_end8, group_lr_scale, group_weight_decay, (int)n_groups, lr, beta1,
-                     beta2, eps, (float)(sqrt(bc2) / bc1), grad_scale, grad_sqnorm, clip_norm);
-  OP_LAUNCH_CHECK();
-  return OP_OK;
+  OP_CHECK_ARG(master, "adamw_groups_master: null pointer");
+  return adamw_launch("adamw_groups_master", true, p, master, g, m, v, nullptr, numel, group_end8, group_lr_scale,
+                      group_weight_decay, n_groups, lr, beta1, beta2, eps, 0.f, step, grad_scale, grad_sqnorm, clip_norm, 0.f, 0.f,
+                      stream);
 }
 
 // One EMA update of a flat fp32 shadow from the flat bf16 parameters (include/onepeace_hip.h): 10 B/param.
@@ -1225,24 +1104,9 @@ int op_adamw_step_groups_ema(void* p, float* master, const void* g, float* m, fl
                              const int64_t* group_end8, const float* group_lr_scale, const float* group_weight_decay,
                              int64_t n_groups, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
                              const float* grad_sqnorm, float clip_norm, float ema_keep, float ema_take, void* stream) {
-  OP_CHECK_ARG(p && g && m && v && ema && group_end8 && group_lr_scale && group_weight_decay, "adamw_groups_ema: null pointer");
-  OP_CHECK_ARG(numel % 8 == 0 && step >= 1 && n_groups >= 1 && n_groups <= ADAM_MAX_GROUPS,
-               "adamw_groups_ema: numel %% 8 == 0, step >= 1, 1 <= n_groups <= %d required", ADAM_MAX_GROUPS);
-  OP_CHECK_ARG(master == nullptr || (ema + numel <= master || master + numel <= ema), "adamw_groups_ema: ema overlaps master");
-  if (numel == 0) return OP_OK;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float bias_corr = (float)(sqrt(bc2) / bc1);
-  if (master)
-    hipLaunchKernelGGL(adamw_groups_ema_kernel<true>, dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p, master,
-                       (const bf16_t*)g, m, v, ema, numel / 8, group_end8, group_lr_scale, group_weight_decay, (int)n_groups, lr,
-                       beta1, beta2, eps, bias_corr, grad_scale, grad_sqnorm, clip_norm, ema_keep, ema_take);
-  else
-    hipLaunchKernelGGL(adamw_groups_ema_kernel<false>, dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p,
-                       (float*)nullptr, (const bf16_t*)g, m, v, ema, numel / 8, group_end8, group_lr_scale, group_weight_decay,
-                       (int)n_groups, lr, beta1, beta2, eps, bias_corr, grad_scale, grad_sqnorm, clip_norm, ema_keep, ema_take);
-  OP_LAUNCH_CHECK();
-  return OP_OK;
+  OP_CHECK_ARG(ema, "adamw_groups_ema: null pointer");
+  return adamw_launch("adamw_groups_ema", true, p, master, g, m, v, ema, numel, group_end8, group_lr_scale, group_weight_decay,
+                      n_groups, lr, beta1, beta2, eps, 0.f, step, grad_scale, grad_sqnorm, clip_norm, ema_keep, ema_take, stream);
 }
 
 // transposed != 0 writes out[h][key][query] (the image the dK/dV kernel reads) instead of out[h][query][key]

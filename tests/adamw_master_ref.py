@@ -1,5 +1,5 @@
 """Shared by tests/test_adamw_master_cpu.py and tests/test_adamw_master_gpu.py: AdamW with an fp32 master copy of the bf16
-parameters (csrc/elementwise.hip: adamw_groups_master_kernel; optim.FusedAdamW / TorchAdamW with master_weights=True) on top of the
+parameters (csrc/elementwise.hip: adamw_kernel<GROUPS, MASTER>; optim.FusedAdamW / TorchAdamW with master_weights=True) on top of the
 fp64 statement and the states of tests/adamw_ref.py.  Plain torch on the CPU; nothing here needs a GPU.
 
 Criteria for ONE step from a given state (master_old fp32, g bf16, m, v fp32), for every element, with
@@ -23,6 +23,12 @@ from tests import adamw_ref as R
 
 def bits16(t):
     return t.detach().cpu().contiguous().view(torch.int16)
+
+
+def bits(t):
+    """The bit pattern of a bf16 or fp32 tensor, for comparisons in which a NaN equals itself and -0 differs from 0."""
+    t = t.detach().cpu().contiguous()
+    return t.view(torch.int16) if t.dtype == torch.bfloat16 else t.view(torch.int32)
 
 
 def cast_matches(p, master):
@@ -78,14 +84,14 @@ def make_master_state(n, step, gscale, pscale, seed=0):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# fp32 emulation of adamw_groups_master_kernel's operation order (no FMA contraction), with planted errors
+# fp32 emulation of the operation order of adamw_kernel<GROUPS, MASTER> (no FMA contraction), with planted errors
 # ------------------------------------------------------------------------------------------------------------------
 PLANTED = ("master_read_from_bf16_p", "p_rounded_before_decay", "master_stored_as_bf16")
 
 
 def emulate_master_fp32(master, p, g, m, v, step, lr, beta1, beta2, eps, grad_scale=1.0, clip_norm=0.0, sqnorm=None, lr_scale=1.0,
                         weight_decay=0.0, planted=None):
-    """Returns (master', p' bf16, m', v').  The expressions are adamw_ref.emulate_fp32's for adamw_groups_kernel, with the master
+    """Returns (master', p' bf16, m', v').  The expressions are adamw_ref.emulate_fp32's for the group tables, with the master
     in the place of float(p)."""
     F = lambda x: torch.tensor(x, dtype=torch.float32) if not torch.is_tensor(x) else x.float()  # noqa: E731
     lr, b1, b2, eps, gs = F(lr), F(beta1), F(beta2), F(eps), F(grad_scale)

@@ -1,5 +1,5 @@
 """Shared by tests/test_adamw_ref_cpu.py, tests/test_adamw_fp64_gpu.py and the AdamW tests of tests/test_ops_gpu.py: the fused
-AdamW step (csrc/elementwise.hip: adamw_kernel, adamw_groups_kernel) and the global gradient norm (sqnorm_*_kernel) stated in fp64,
+AdamW step (csrc/elementwise.hip: adamw_kernel<GROUPS, MASTER, EMA>) and the global gradient norm (sqnorm_*_kernel) stated in fp64,
 the acceptance criteria for ONE step from a given state, an fp32 emulation of the kernels' operation order with planted errors,
 and the seeded states and case lists.  Plain torch on the CPU; nothing here needs a GPU.
 
@@ -219,7 +219,7 @@ PLANTED = ("decay_after_update", "eps_inside_sqrt", "bias_of_previous_step", "cl
 
 def emulate_fp32(p, g, m, v, step, lr, beta1, beta2, eps, grad_scale=1.0, clip_norm=0.0, sqnorm=None, lr_scale=None,
                  weight_decay=0.0, planted=None):
-    """What adamw_kernel (lr_scale None) or adamw_groups_kernel (lr_scale and weight_decay per element) computes, in torch fp32 on the
+    """What adamw_kernel computes without GROUPS (lr_scale None) or with it (lr_scale and weight_decay per element), in torch fp32 on the
     CPU: returns (p bf16, m, v).  sqnorm: an fp32 scalar as op_sqnorm leaves it (default: the fp64 sum rounded to fp32)."""
     F = lambda x: torch.tensor(x, dtype=torch.float32) if not torch.is_tensor(x) else x.float()  # noqa: E731
     lr, b1, b2, eps, gs = F(lr), F(beta1), F(beta2), F(eps), F(grad_scale)
@@ -249,7 +249,7 @@ def emulate_fp32(p, g, m, v, step, lr, beta1, beta2, eps, grad_scale=1.0, clip_n
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# group tables (lists of vector counts) for adamw_groups_kernel
+# group tables (lists of vector counts) for adamw_kernel<GROUPS = true>
 # ------------------------------------------------------------------------------------------------------------------
 # boundaries mid-wave and mid-workgroup; one-vector groups first, in the middle and last; one group longer than a grid stride
 # (524 288 vectors), so a thread's second vector lies in another group than its first, and for some threads in the same one
@@ -262,6 +262,23 @@ def group_tables(n_groups, weight_decay=0.05):
     """lr scales 0.65^(k mod 12) and decay alternating on / off: two adjacent groups never share both values, so an off-by-one in
     the lookup changes every boundary vector.  (The exponent wraps so that the scales of a long table stay in fp32's range.)"""
     return [0.65 ** (k % 12) for k in range(n_groups)], [weight_decay if k % 2 == 0 else 0.0 for k in range(n_groups)]
+
+
+def device_group_tables(counts, device="cuda"):
+    """group_tables for a list of vector counts as the entries take them: (end8 int64, lr scale fp32, weight decay fp32) on `device`."""
+    scale, wd = group_tables(len(counts))
+    end8 = torch.cumsum(torch.tensor(counts, dtype=torch.int64), 0)
+    return end8.to(device), torch.tensor(scale, dtype=torch.float32, device=device), torch.tensor(wd, dtype=torch.float32, device=device)
+
+
+class TwoStrides(torch.nn.Module):
+    """2 * STRIDE + 8 * 773 parameters: a decayed matrix of two grid strides and a vector without decay."""
+
+    def __init__(self):
+        super().__init__()
+        gen = torch.Generator().manual_seed(7)
+        self.mat = torch.nn.Parameter(torch.randn(2048, 4096, generator=gen))
+        self.vec = torch.nn.Parameter(torch.randn(8 * 773, generator=gen))
 
 
 # ------------------------------------------------------------------------------------------------------------------

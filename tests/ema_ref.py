@@ -1,5 +1,5 @@
 """Shared by tests/test_ema_cpu.py and tests/test_ema_gpu.py: the fp32 weight average (one-peace_amd/ema.py; csrc/elementwise.hip:
-ema_step_kernel, adamw_groups_ema_kernel) stated in fp64, its acceptance criterion, an fp32 emulation with planted faults and the
+ema_step_kernel, adamw_kernel<GROUPS, MASTER, EMA>) stated in fp64, its acceptance criterion, an fp32 emulation with planted faults and the
 seeded states, on top of tests/adamw_ref.py and tests/adamw_master_ref.py.  Plain torch on the CPU; nothing here needs a GPU.
 
 The rule:   e' = keep e + take p^      keep = float32(decay), take = float32(1.0 - decay) (the subtraction in double), p^ the bf16
@@ -104,6 +104,22 @@ def make_ema_state(n, step, seed=0, clip=None):
     e = ((e.view(torch.int32) & ~0xFFFF) | low).view(torch.float32).clone()
     assert bool(torch.isfinite(e).all())
     return master, p, g, m, v, e
+
+
+_STATES = {}
+
+
+def case_state(n, step, clip):
+    """Host state of a one-step case, built once and shared by the GPU tests (they work on copies): master, p, g, m, v, e
+    (+ grad_scale, clip_norm)."""
+    key = (n, step, clip)
+    if key not in _STATES:
+        gs, clip_norm = (0.25, R.CLIP_NORM) if clip else (1.0, 0.0)
+        st = make_ema_state(n, step, seed=2, clip=(gs, "above") if clip else None)
+        if clip:
+            R.assert_clip_landing(st[2], gs, "above")
+        _STATES[key] = st + (gs, clip_norm)
+    return _STATES[key]
 
 
 def changed_share(p_new, p_old):

@@ -1,4 +1,4 @@
-"""The optimiser kernels (csrc/elementwise.hip: adamw_kernel, adamw_groups_kernel, sqnorm_partial_kernel, sqnorm_final_kernel) against
+"""The optimiser kernels (csrc/elementwise.hip: adamw_kernel without and with GROUPS, sqnorm_partial_kernel, sqnorm_final_kernel) against
 the fp64 statement of tests/adamw_ref.py, one step at a time from a given state, under the criteria derived there: the stored bf16
 parameter inside [bf16(ref - delta), bf16(ref + delta)] for EVERY element, the moments within 4 fp32 roundings of the magnitudes
 they sum, the sum of squares within its summation bound and bit-reproducible.  Every case first asserts, on the reference alone,
@@ -141,12 +141,6 @@ GROUP_CASES = [("awkward", R.AWKWARD_GROUPS, t, clip) for t in (1, 1000) for cli
     ("single%d" % n, (n // 8,), t, clip) for n, t, clip in zip(R.SIZES, (1, 1000, 1, 1000), (False, True, True, False))]
 
 
-def _group_tables(counts):
-    scale, wd = R.group_tables(len(counts))
-    end8 = torch.cumsum(torch.tensor(counts, dtype=torch.int64), 0)
-    return end8.to(DEV), torch.tensor(scale, dtype=torch.float32, device=DEV), torch.tensor(wd, dtype=torch.float32, device=DEV)
-
-
 @pytest.mark.parametrize("name,counts,step,clip", GROUP_CASES, ids=lambda x: None if isinstance(x, tuple) else str(x))
 def test_adamw_step_groups_against_fp64(name, counts, step, clip):
     hip = hipmod()
@@ -155,7 +149,7 @@ def test_adamw_step_groups_against_fp64(name, counts, step, clip):
     lr, b1, b2, eps, _ = R.HYPER[0]
     gs, clip_norm = (0.25, R.CLIP_NORM) if clip else (1.0, 0.0)
     p, g, m, v = R.make_state(n, step, 1e-2, 1.0, seed=2)
-    end8, scale, wd = _group_tables(counts)
+    end8, scale, wd = R.device_group_tables(counts)
     pd, gd, md, vd = to_dev(p, g, m, v)
     sq = used = None
     if clip:
@@ -176,7 +170,7 @@ def test_adamw_step_groups_rejects_257_groups():
     counts = (1,) * 257
     n = 8 * len(counts)
     p, g, m, v = R.make_state(n, 2, 1e-2, 1.0, seed=3)
-    end8, scale, wd = _group_tables(counts)
+    end8, scale, wd = R.device_group_tables(counts)
     pd, gd, md, vd = to_dev(p, g, m, v)
     lr, b1, b2, eps, _ = R.HYPER[0]
     with pytest.raises(RuntimeError):
@@ -257,23 +251,13 @@ def test_fused_adamw_five_steps_against_fp64(clip_norm):
 
 
 # ------------------------------------------------------------------------------------------------------------------ e
-class TwoStrides(torch.nn.Module):
-    """2 * STRIDE + 8 * 773 parameters: a decayed matrix of two grid strides and a vector without decay."""
-
-    def __init__(self):
-        super().__init__()
-        gen = torch.Generator().manual_seed(7)
-        self.mat = torch.nn.Parameter(torch.randn(2048, 4096, generator=gen))
-        self.vec = torch.nn.Parameter(torch.randn(8 * 773, generator=gen))
-
-
 _BIG = {}
 
 
 def _big():
     """One module, its gradients and its fp64-ready CPU copies for all cases of (e); the cases work on copies."""
     if not _BIG:
-        model = TwoStrides().to(torch.bfloat16)
+        model = R.TwoStrides().to(torch.bfloat16)
         g = (torch.randn(R.SIZES[3], generator=torch.Generator().manual_seed(8)) * 1e-2).to(torch.bfloat16)
         _BIG.update(model=model, g=g)
     return _BIG["model"], _BIG["g"]

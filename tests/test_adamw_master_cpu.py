@@ -1,7 +1,7 @@
 """AdamW with an fp32 master copy, without a GPU: optim.TorchAdamW(master_weights=True) -- the readable statement of the rule and
 the CPU route -- against the fp64 statement of tests/adamw_ref.py under the criteria of tests/adamw_master_ref.py; the two
 100-step cases whose updates the bf16-only arrangement rounds away; the criteria themselves against an fp32 emulation of
-adamw_groups_master_kernel's order with planted errors; the reference's FP16Optimizer arithmetic (tests/golden/adamw_master.pt);
+the order of adamw_kernel<GROUPS, MASTER> with planted errors; the reference's FP16Optimizer arithmetic (tests/golden/adamw_master.pt);
 sync_master(), the ABI entry, and FusedAdamW's refusal to run without a GPU."""
 import ctypes
 import os

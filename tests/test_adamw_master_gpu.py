@@ -1,12 +1,13 @@
-"""AdamW with an fp32 master copy on the device (csrc/elementwise.hip: adamw_groups_master_kernel through hip.adamw_step_groups_master and
-optim.FusedAdamW(master_weights=True)) under the criteria of tests/adamw_master_ref.py: for EVERY element the stored master within
+"""AdamW with an fp32 master copy on the device (csrc/elementwise.hip: adamw_kernel<GROUPS, MASTER> through hip.adamw_step_groups_master
+and optim.FusedAdamW(master_weights=True)) under the criteria of tests/adamw_master_ref.py: for EVERY element the stored master within
 delta of the fp64 step from the old master, the stored bf16 parameter bit-identical to the round-to-nearest-even cast of the stored
 master, the moments inside their bounds.
 
   a  one step: adamw_ref.SIZES as a single group, the awkward and the full (256) group tables, steps 1 and 1000, with and without
      clipping (the device's own sum of squares goes into the reference).  The master has a non-zero low half in every element and the
      result must differ from what the bf16 parameter would have given; the parameter buffer holds NaNs before the call (it is never
-     read); every buffer sits between guard regions
+     read); every buffer sits between guard regions.  And from a master that IS float(p): p, m and v bit-identical to what
+     hip.adamw_step_groups stores from the same inputs
   b  refused calls: 257 groups, a null master -- nothing launched, nothing written
   c  the two 100-step cases through FusedAdamW, with and without the master
   d  tests/golden/adamw_master.pt (the reference's FP16Optimizer arithmetic) through FusedAdamW(master_weights=True)
@@ -20,6 +21,7 @@ import torch
 
 from tests import adamw_master_ref as M
 from tests import adamw_ref as R
+from tests import ema_ref as E
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -46,12 +48,6 @@ class Guarded:
         return bool((w[:GUARD] == self.canary).all()) and bool((w[-GUARD:] == self.canary).all())
 
 
-def _group_tables(counts):
-    scale, wd = R.group_tables(len(counts))
-    end8 = torch.cumsum(torch.tensor(counts, dtype=torch.int64), 0)
-    return end8.to(DEV), torch.tensor(scale, dtype=torch.float32, device=DEV), torch.tensor(wd, dtype=torch.float32, device=DEV)
-
-
 # ------------------------------------------------------------------------------------------------------------------ a
 CASES = [("awkward", R.AWKWARD_GROUPS, t, clip) for t in (1, 1000) for clip in (False, True)] + [
     ("full", R.FULL_GROUPS, t, clip) for t in (1, 1000) for clip in (False, True)] + [
@@ -70,7 +66,7 @@ def test_master_step_against_fp64(name, counts, step, clip):
     if clip:  # the clip states of adamw_ref.py: the scaled norm 40 x the threshold, moments at the scale of the clipped gradient
         _, g, m, v = R.make_clip_state(n, gs, "above", step, seed=2)
         R.assert_clip_landing(g, gs, "above")
-    end8, scale, wd = _group_tables(counts)
+    end8, scale, wd = R.device_group_tables(counts)
     G = {k: Guarded(t) for k, t in dict(p=torch.full_like(p, float("nan")), master=master, g=g, m=m, v=v).items()}
     sq = None
     if clip:
@@ -92,12 +88,40 @@ def test_master_step_against_fp64(name, counts, step, clip):
     assert float(apart) >= 0.99, "%s: only %.4f of the masters differ from a step taken from the bf16 parameter" % (what, float(apart))
 
 
+@pytest.mark.parametrize("name,counts,step,clip", CASES, ids=lambda x: None if isinstance(x, tuple) else str(x))
+def test_master_step_matches_the_plain_step_bit_for_bit(name, counts, step, clip):
+    """With master == float(p) both routes start the update from the same fp32 number, so they must store the same p, m and v: the
+    link between hip.adamw_step_groups and hip.adamw_step_groups_master that test_ema_gpu.py's bitwise test (whose states, buffers and
+    changed-share condition this follows) has for the fused entry.  adamw_master_ref.emulate_master_fp32 from these states changes
+    0.993 ... 1.000 of the bf16 parameters on the CPU, so neither route passes by leaving p alone."""
+    hip = hipmod()
+    what = "%s-t%d-%s" % (name, step, "clip" if clip else "noclip")
+    lr, b1, b2, eps, _ = R.HYPER[0]
+    _, p, g, m, v, _, gs, clip_norm = E.case_state(8 * sum(counts), step, clip)
+    hyper = R.device_group_tables(counts) + (lr, b1, b2, eps, step)
+    plain = {k: Guarded(t) for k, t in dict(p=p, g=g, m=m, v=v).items()}
+    mast = {k: Guarded(t) for k, t in dict(p=torch.full_like(p, float("nan")), master=p.float(), g=g, m=m, v=v).items()}
+    sq = hip.sqnorm(plain["g"].t) if clip else None
+    hip.adamw_step_groups(plain["p"].t, plain["g"].t, plain["m"].t, plain["v"].t, *hyper, gs, sq, clip_norm)
+    hip.adamw_step_groups_master(mast["p"].t, mast["master"].t, mast["g"].t, mast["m"].t, mast["v"].t, *hyper, gs, sq, clip_norm)
+    torch.cuda.synchronize()
+    for route, G in (("plain", plain), ("master", mast)):
+        for k, b in G.items():
+            assert b.intact(), "%s: the guard regions of %s (%s route) were written" % (what, k, route)
+        assert torch.equal(M.bits(G["g"].t), M.bits(g)), "%s: the %s route wrote the gradient buffer" % (what, route)
+    for k in ("p", "m", "v"):
+        assert torch.equal(M.bits(mast[k].t), M.bits(plain[k].t)), "%s: %s differs between the master and the plain route" % (what, k)
+    assert M.cast_matches(mast["p"].t, mast["master"].t) == 0, "%s: p is not bf16(master)" % what
+    share = E.changed_share(plain["p"].t, p)
+    assert share >= 0.9, "%s: only %.3f of the bf16 parameters changed in the step" % (what, share)
+
+
 # ------------------------------------------------------------------------------------------------------------------ b
 def _refusal_state(n_groups):
     counts = (1,) * n_groups
     master, p, g, m, v = M.make_master_state(8 * n_groups, 2, 1e-2, 1.0, seed=3)
     host = dict(p=p, master=master, g=g, m=m, v=v)
-    return host, {k: t.to(DEV) for k, t in host.items()}, _group_tables(counts)
+    return host, {k: t.to(DEV) for k, t in host.items()}, R.device_group_tables(counts)
 
 
 def _untouched(host, dev):
@@ -193,16 +217,6 @@ def test_sync_master_on_the_device():
 
 
 # ------------------------------------------------------------------------------------------------------------------ f
-class TwoStrides(torch.nn.Module):
-    """2 * STRIDE + 8 * 773 parameters: a decayed matrix of two grid strides and a vector without decay."""
-
-    def __init__(self):
-        super().__init__()
-        gen = torch.Generator().manual_seed(7)
-        self.mat = torch.nn.Parameter(torch.randn(2048, 4096, generator=gen))
-        self.vec = torch.nn.Parameter(torch.randn(8 * 773, generator=gen))
-
-
 _BIG = {}
 POS = R.STRIDE + 8 * 12345 + 3  # in the second grid stride
 LR, B1, B2, EPS, WD0 = 5e-4, 0.9, 0.98, 1e-6, 0.05
@@ -214,7 +228,7 @@ def _big_opt(step):
     from one_peace_amd.optim import FusedAdamW
     n = R.SIZES[3]
     if not _BIG:
-        _BIG["model"] = TwoStrides().to(torch.bfloat16)
+        _BIG["model"] = R.TwoStrides().to(torch.bfloat16)
         _BIG["state"] = M.make_master_state(n, 1000, 1e-2, 1.0, seed=8)
     flat = FlatParameters(copy.deepcopy(_BIG["model"]).to(DEV))
     assert flat.numel == n

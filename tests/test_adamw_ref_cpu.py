@@ -93,7 +93,7 @@ def test_adamw_fp64_agrees_with_torch_adamw_over_flat_parameters(clip):
 
 
 def _emulated(p, g, m, v, step, lr, b1, b2, eps, planted=None, groups=False, **kw):
-    if groups:  # the arithmetic of adamw_groups_kernel: lr * lr_scale and the decay multiplier formed per group in fp32
+    if groups:  # the arithmetic of adamw_kernel<GROUPS = true>: lr * lr_scale and the decay multiplier formed per group in fp32
         n = p.numel()
         kw = dict(kw, lr_scale=torch.ones(n) if "lr_scale" not in kw else kw["lr_scale"],
                   weight_decay=torch.as_tensor(kw.get("weight_decay", 0.0), dtype=torch.float32).expand(n))

@@ -1,4 +1,4 @@
-"""The fp32 weight average on the device (csrc/elementwise.hip: ema_step_kernel through hip.ema_step, adamw_groups_ema_kernel<MASTER>
+"""The fp32 weight average on the device (csrc/elementwise.hip: ema_step_kernel through hip.ema_step, adamw_kernel<true, MASTER, true>
 through hip.adamw_step_groups_ema, ema.FlatEMA, optim.FusedAdamW(ema=)) under the criterion of tests/ema_ref.py.
 
   a  hip.ema_step against fp64 for every element: adamw_ref.SIZES x decay 0.9999 / 0.99 / 0; guards intact, p unwritten; decay 0 copies
@@ -19,31 +19,16 @@ import torch
 from tests import adamw_master_ref as M
 from tests import adamw_ref as R
 from tests import ema_ref as E
-from tests.test_adamw_master_gpu import DEV, Guarded, _group_tables, hipmod
+from tests.test_adamw_master_gpu import DEV, Guarded, hipmod
 
 pytestmark = pytest.mark.gpu
-
-_STATES = {}
-
-
-def _state(n, step, clip):
-    """Host state of a case, built once: master, p, g, m, v, e (+ grad_scale, clip_norm)."""
-    key = (n, step, clip)
-    if key not in _STATES:
-        gs, clip_norm = (0.25, R.CLIP_NORM) if clip else (1.0, 0.0)
-        st = E.make_ema_state(n, step, seed=2, clip=(gs, "above") if clip else None)
-        if clip:
-            R.assert_clip_landing(st[2], gs, "above")
-        _STATES[key] = st + (gs, clip_norm)
-    return _STATES[key]
-
 
 # ------------------------------------------------------------------------------------------------------------------ a
 @pytest.mark.parametrize("decay", [0.9999, 0.99, 0.0])
 @pytest.mark.parametrize("n", R.SIZES)
 def test_ema_step_against_fp64(n, decay):
     hip = hipmod()
-    _, p, _, _, _, e, _, _ = _state(n, 1000, False)
+    _, p, _, _, _, e, _, _ = E.case_state(n, 1000, False)
     keep, take = E.coefficients(decay)
     G = {"e": Guarded(e), "p": Guarded(p)}
     hip.ema_step(G["e"].t, G["p"].t, keep, take)
@@ -63,11 +48,6 @@ CASES = [("awkward", R.AWKWARD_GROUPS, t, clip) for t in (1, 1000) for clip in (
     ("single%d" % n, (n // 8,), t, clip) for n in R.SIZES for t in (1, 1000) for clip in (False, True)]
 
 
-def _bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int16) if t.dtype == torch.bfloat16 else t.view(torch.int32)
-
-
 @pytest.mark.parametrize("with_master", [False, True], ids=["plain", "master"])
 @pytest.mark.parametrize("name,counts,step,clip", CASES, ids=lambda x: None if isinstance(x, tuple) else str(x))
 def test_fused_step_matches_the_unfused_pair_bit_for_bit(name, counts, step, clip, with_master):
@@ -75,10 +55,10 @@ def test_fused_step_matches_the_unfused_pair_bit_for_bit(name, counts, step, cli
     what = "%s-t%d-%s-%s" % (name, step, "clip" if clip else "noclip", "master" if with_master else "plain")
     n = 8 * sum(counts)
     lr, b1, b2, eps, _ = R.HYPER[0]
-    master, p, g, m, v, e, gs, clip_norm = _state(n, step, clip)
+    master, p, g, m, v, e, gs, clip_norm = E.case_state(n, step, clip)
     decay = 0.99 if step == 1 else 0.9999
     keep, take = E.coefficients(decay)
-    end8, scale, wd = _group_tables(counts)
+    end8, scale, wd = R.device_group_tables(counts)
     p_in = torch.full_like(p, float("nan")) if with_master else p  # with a master the parameter buffer is never read
     hyper = (end8, scale, wd, lr, b1, b2, eps, step)
 
@@ -99,19 +79,19 @@ def test_fused_step_matches_the_unfused_pair_bit_for_bit(name, counts, step, cli
         torch.cuda.synchronize()
         for k, b in G.items():
             assert b.intact(), "%s: the guard regions of %s were written" % (what, k)
-        runs.append({k: _bits(b.t) for k, b in G.items()})
+        runs.append({k: M.bits(b.t) for k, b in G.items()})
     got, again = runs
     new_p = G["p"].t.cpu()
     # (i) the optimiser's part is what the unfused entry stores
     for k in ("p", "m", "v") + (("master",) if with_master else ()):
-        assert torch.equal(got[k], _bits(u[k])), "%s: %s differs from the unfused entry" % (what, k)
+        assert torch.equal(got[k], M.bits(u[k])), "%s: %s differs from the unfused entry" % (what, k)
     if not with_master:
-        assert torch.equal(got["master"], _bits(master)), "%s: the master buffer was written without a master" % what
+        assert torch.equal(got["master"], M.bits(master)), "%s: the master buffer was written without a master" % what
     # (ii) the average is what ema_step makes of that p, and inside the criterion
-    assert torch.equal(got["e"], _bits(u["e"])), "%s: the average differs from hip.ema_step on the new parameters" % what
+    assert torch.equal(got["e"], M.bits(u["e"])), "%s: the average differs from hip.ema_step on the new parameters" % what
     E.assert_step(G["e"].t, e, new_p, keep, take, what)
     # (iii)
-    assert torch.equal(got["g"], _bits(g)), "%s: the gradient buffer was written" % what
+    assert torch.equal(got["g"], M.bits(g)), "%s: the gradient buffer was written" % what
     # (iv) a stale parameter would show: the step changed the bf16 value of (nearly) every element
     share = E.changed_share(new_p, p)
     assert share >= 0.9, "%s: only %.3f of the bf16 parameters changed in the step" % (what, share)
@@ -125,11 +105,11 @@ def _refusal_state(n_groups):
     counts = (1,) * n_groups
     master, p, g, m, v, e = E.make_ema_state(8 * n_groups, 2, seed=3)
     host = dict(p=p, master=master, g=g, m=m, v=v, e=e)
-    return host, {k: t.to(DEV) for k, t in host.items()}, _group_tables(counts)
+    return host, {k: t.to(DEV) for k, t in host.items()}, R.device_group_tables(counts)
 
 
 def _untouched(host, dev):
-    return all(torch.equal(_bits(dev[k]), _bits(host[k])) for k in host)
+    return all(torch.equal(M.bits(dev[k]), M.bits(host[k])) for k in host)
 
 
 def _fused(hip, d, tables, master, ema, sl=slice(None), groups=slice(None)):
@@ -173,10 +153,10 @@ def test_fused_step_rejects_an_average_that_overlaps_the_master():
     with pytest.raises(RuntimeError):
         _fused(hip, d, tables, both[:128], both[64:192])
     torch.cuda.synchronize()
-    assert _untouched(host, d) and torch.equal(_bits(both), _bits(before))
+    assert _untouched(host, d) and torch.equal(M.bits(both), M.bits(before))
     _fused(hip, d, tables, both[:128], both[128:])  # adjacent is not overlapping
     torch.cuda.synchronize()
-    assert not torch.equal(_bits(both[128:]), _bits(before[128:]))
+    assert not torch.equal(M.bits(both[128:]), M.bits(before[128:]))
 
 
 def test_the_wrappers_reject_an_average_that_does_not_cover_the_parameters():
@@ -268,7 +248,7 @@ def test_applied_on_the_device_refreshes_the_cached_transposed_weights():
     pick = torch.eye(64, device=DEV)[:16].to(torch.bfloat16)
     o = {n: o for n, _, o, _ in flat.entries}["weight"]
     with ema.applied():
-        assert torch.equal(_bits(flat.params), _bits(want))
+        assert torch.equal(M.bits(flat.params), M.bits(want))
         avg_w = want[o:o + 64 * 128].view(128, 64)
         assert torch.equal(model.weight.detach(), avg_w)
         inside = ops._transposed(model.weight)
@@ -276,8 +256,8 @@ def test_applied_on_the_device_refreshes_the_cached_transposed_weights():
         # a forward with one-hot rows picks single weights: exact whatever GEMM runs it
         assert torch.equal(pick @ inside, avg_w.t()[:16]) and torch.equal(torch.nn.functional.linear(pick, model.weight), avg_w.t()[:16])
     torch.cuda.synchronize()
-    assert torch.equal(_bits(flat.params), _bits(before)), "the parameters did not come back bit for bit"
-    assert torch.equal(_bits(opt.master), _bits(master)), "the master was touched"
+    assert torch.equal(M.bits(flat.params), M.bits(before)), "the parameters did not come back bit for bit"
+    assert torch.equal(M.bits(opt.master), M.bits(master)), "the master was touched"
     assert torch.equal(ops._transposed(model.weight), before[o:o + 64 * 128].view(128, 64).t()), "the caches were not refreshed on exit"
     assert torch.equal(ema.shadow.to(torch.bfloat16), want)
 
@@ -299,7 +279,7 @@ def _poisoned(master_weights, value):
     from one_peace_amd.ema import FlatEMA
     from one_peace_amd.optim import FusedAdamW
     n = R.SIZES[2]
-    _, p, g, _, _, e, _, _ = _state(n, 1, False)
+    _, p, g, _, _, e, _, _ = E.case_state(n, 1, False)
     flat = FlatParameters(OneVector().to(DEV).to(torch.bfloat16), no_decay=lambda name, q: False)
     with torch.no_grad():
         flat.params.copy_(p)

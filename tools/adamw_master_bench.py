@@ -1,4 +1,4 @@
-"""The fused AdamW step with and without the fp32 master copy (csrc/elementwise.hip: adamw_groups_kernel, adamw_groups_master_kernel).
+"""The fused AdamW step with and without the fp32 master copy (csrc/elementwise.hip: adamw_kernel<GROUPS, MASTER>).
 
     python tools/adamw_master_bench.py [--numel 3890000000] [--groups 84] [--launches 25] [--warmup 5] [--out FILE]
     python tools/adamw_master_bench.py --lost-updates [--lr 5e-4 2e-4 7e-5 8.5e-6 9.3e-7] [--steps 1 10]

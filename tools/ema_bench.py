@@ -1,5 +1,5 @@
 """The fp32 weight average (ema.FlatEMA) beside the fused AdamW step: what each way of keeping it costs (csrc/elementwise.hip:
-ema_step_kernel, adamw_groups_ema_kernel<MASTER>).
+ema_step_kernel, adamw_kernel<GROUPS, MASTER, EMA>).
 
     python tools/ema_bench.py [--numel 3890000000] [--groups 84] [--launches 25] [--warmup 5] [--layers 40] [--out FILE]
 

@@ -15,7 +15,7 @@ def load(d, counter):
     f = glob.glob(d + "/**/*counter_collection.csv", recursive=True)[0]
     agg = defaultdict(lambda: [0.0, 0])
     for r in csv.DictReader(open(f)):
-        m = re.search(r"(ln_geglu_bwd|ln_geglu_fwd|ln_bwd|ln_fwd|resid_bwd|adamw_groups|colsum_partial)", r["Kernel_Name"])
+        m = re.search(r"(ln_geglu_bwd|ln_geglu_fwd|ln_bwd|ln_fwd|resid_bwd|adamw_kernel|colsum_partial)", r["Kernel_Name"])
         if m:
             agg[m.group(1)][0] += float(r["Counter_Value"]); agg[m.group(1)][1] += 1
     return agg
@@ -23,7 +23,7 @@ def durations(d):
     f = glob.glob(d + "/**/*kernel_trace.csv", recursive=True)[0]
     agg = defaultdict(float)
     for r in csv.DictReader(open(f)):
-        m = re.search(r"(ln_geglu_bwd|ln_geglu_fwd|ln_bwd|ln_fwd|resid_bwd|adamw_groups|colsum_partial)", r["Kernel_Name"])
+        m = re.search(r"(ln_geglu_bwd|ln_geglu_fwd|ln_bwd|ln_fwd|resid_bwd|adamw_kernel|colsum_partial)", r["Kernel_Name"])
         if m:
             agg[m.group(1)] += (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-6
     return agg
