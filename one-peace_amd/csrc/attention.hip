@@ -2769,21 +2769,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dbias_kernel(AttnBwdArgs p) {
 //                 bit 1 = round 2's batch-chunk rule of the merged kernel (A/B timing); bits 2-3 = 2: dK/dV kernel with 64 keys per workgroup;
 //                 bits 4-9 = forced number of batch chunks of the merged kernel (sweep of tools/attn_chunks_ab.py: the rule's choice is
 //                 within 1 % of the best of {2 ... 16} at S = 257 / 250 / 65); bit 10 = no persistent dQ (+ dBias) kernel (193 ... 257
-//                 tokens then run the kernels of rounds 1-3: tests / A-B timing)
+//                 tokens then run the kernels of rounds 1-3: tests / A-B timing); bit 11 = dK/dV: a trailing key block of <= 16 keys is
+//                 NOT split over the waves by queries; bit 12 = the dK/dV kernel of rounds 1-3 instead of the persistent one;
+//                 bit 13 = the persistent dK/dV kernel at S = 256 too (two full key workgroups: nothing to gain, +5 %)
+enum : int64_t {
+  FWD_STREAMING = 1 << 0, FWD_ABLATE_SHIFT = 1, FWD_ABLATE_MASK = 3, FWD_WAVES_SHIFT = 3, FWD_WAVES_MASK = 15, FWD_NO_PERS = 1 << 7,
+  BWD_SEPARATE_DBIAS = 1 << 0, BWD_ROUND2_CHUNKS = 1 << 1, BWD_DKDV_KEYS_SHIFT = 2, BWD_DKDV_KEYS_MASK = 3, BWD_CHUNKS_SHIFT = 4,
+  BWD_CHUNKS_MASK = 63, BWD_NO_PERS_DQ = 1 << 10, BWD_NO_LONE_KEYS = 1 << 11, BWD_NO_PERS_DKDV = 1 << 12, BWD_PERS_DKDV_256 = 1 << 13,
+};
 
-template <bool HAS_BIAS, bool HAS_PAD>
-int launch_fwd_res(const AttnArgs& a, const bf16_t* frag, dim3 grid, int nw, size_t sh, int rows_pad, int qb_per_wg, int abl,
-                   hipStream_t s) {
-  OP_ENSURE_LDS((attn_fwd_res_kernel<HAS_BIAS, HAS_PAD>), 2 * RES_MAX_S * 128, "attn_fwd");
-  hipLaunchKernelGGL((attn_fwd_res_kernel<HAS_BIAS, HAS_PAD>), grid, dim3(nw * 64), sh, s, a, frag, rows_pad, qb_per_wg, abl);
-  return OP_OK;
-}
-
-template <bool HAS_BIAS, bool HAS_PAD>
-int launch_fwd_pers(const AttnArgs& a, const bf16_t* frag, int nwg, size_t sh, int rows_pad, int nitems, hipStream_t s) {
-  OP_ENSURE_LDS((attn_fwd_pers_kernel<HAS_BIAS, HAS_PAD>), 4 * PERS_MAX_ROWS * 128 + 2 * PERS_NW * PERS_SCR * 4, "attn_fwd");
-  hipLaunchKernelGGL((attn_fwd_pers_kernel<HAS_BIAS, HAS_PAD>), dim3(nwg), dim3(PERS_NW * 64), sh, s, a, frag, rows_pad, nitems);
-  return OP_OK;
+// f(HAS_BIAS, HAS_PAD) (as std::bool_constant): the mask template flags of every attention kernel
+template <typename F> int with_bias_pad(const void* bias, const void* key_pad, F&& f) {
+  return op_with_bool(bias != nullptr, [&](auto hb) { return op_with_bool(key_pad != nullptr, [&](auto hp) { return f(hb, hp); }); });
 }
 
 // number of batch chunks (= dbias slabs) of the merged dQ + dBias kernel; 1 when the separate kernels run.
@@ -2792,19 +2789,6 @@ int launch_fwd_pers(const AttnArgs& a, const bf16_t* frag, int nwg, size_t sh, i
 // ">= 768 workgroups", which at 257 tokens (5 query tiles x 24 heads) gave 7 chunks of 19 samples = 840 workgroups = 1.64 -> 2
 // rounds x 19 = 38 sample-times; 4 chunks of 32 (480 workgroups, one round) or 8 of 16 cost 32.  Chosen here: the chunk count with
 // the smallest cost (+ a little per chunk for the slab read-modify-write at the end of every workgroup; fewer slabs on a tie).
-// CUs of the CURRENT device, cached per device (a process may drive several)
-inline int attn_num_cus() {
-  static int cached[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  if (cached[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cached[dev] = n;
-  }
-  return cached[dev];
-}
-
 inline int dbias_chunks(int64_t B, int64_t S, int64_t heads, bool merge, bool round2_rule = false, int forced = 0) {
   if (!merge || ceil_div(S, BKV) > 6) return 1;
   if (forced > 0) return ceil_div(B, ceil_div(B, min((int64_t)forced, B)));  // (tune bits 4-9: A/B timing)
@@ -2815,7 +2799,7 @@ inline int dbias_chunks(int64_t B, int64_t S, int64_t heads, bool merge, bool ro
     if (chunks > B) chunks = (int)B;
     return ceil_div(B, ceil_div(B, chunks));
   }
-  const int cus = attn_num_cus();
+  const int cus = op_num_cus();
   const int64_t base = (int64_t)ceil_div(S, 64) * heads, slots = 2 * (int64_t)cus;
   int best = 1;
   double best_cost = 1e30;
@@ -2842,48 +2826,29 @@ inline int sep_bchunk(int64_t B, int64_t S, int64_t heads) {
 // one workgroup per CU
 inline int pers_bwd_chunks(int64_t B, int64_t S, int64_t heads) {
   const int nqh = ceil_div(min((int64_t)ceil_div(S, 16), (int64_t)2 * PERS_NW), PERS_NW);
-  int c = (int)(attn_num_cus() / (heads * nqh));
+  int c = (int)(op_num_cus() / (heads * nqh));
   if (c < 1) c = 1;
   if (c > B) c = (int)B;
   return ceil_div(B, ceil_div(B, c));
 }
 inline bool pers_bwd_shape(int64_t S) { return S > 192 && S <= 257; }
 
-template <bool HAS_BIAS, bool HAS_PAD>
-int launch_bwd_dq_pers(const AttnBwdArgs& a, int nwg, size_t sh, int rows_pad, int nqh, hipStream_t s) {
-  if (a.S > 256) {
-    OP_ENSURE_LDS((attn_bwd_dq_pers_kernel<HAS_BIAS, HAS_PAD, 5, 1>), 4 * PERS_MAX_ROWS * 128 + 2 * PERS_NW * 64 * 4, "attn_bwd");
-    hipLaunchKernelGGL((attn_bwd_dq_pers_kernel<HAS_BIAS, HAS_PAD, 5, 1>), dim3(nwg), dim3(PERS_NW * 64), sh, s, a, rows_pad, nqh);
-  } else {
-    OP_ENSURE_LDS((attn_bwd_dq_pers_kernel<HAS_BIAS, HAS_PAD, 4, 4>), 4 * PERS_MAX_ROWS * 128 + 2 * PERS_NW * 64 * 4, "attn_bwd");
-    hipLaunchKernelGGL((attn_bwd_dq_pers_kernel<HAS_BIAS, HAS_PAD, 4, 4>), dim3(nwg), dim3(PERS_NW * 64), sh, s, a, rows_pad, nqh);
-  }
-  return OP_OK;
-}
-
-// persistent dK / dV kernel: one workgroup per CU walks the (sample, head) items
+// persistent dK / dV kernel: 16-key rows and LDS bytes
 inline int dkdv_pers_rows(int64_t S) { return (int)((S + 15) / 16) * 16; }
 inline size_t dkdv_pers_lds(int64_t S) { return (size_t)2 * (2 * dkdv_pers_rows(S) * 128 + 6144) + 2 * PERS_NW * PERS_SCRL * 4; }
-template <bool HAS_BIAS, bool HAS_PAD>
-int launch_bwd_dkdv_pers(const AttnBwdArgs& a, hipStream_t s) {
-  const int rows_pad = dkdv_pers_rows(a.S);
-  const size_t sh = dkdv_pers_lds(a.S);
-  const int nitems = a.B * a.heads;
-  const int nwg = min(nitems, attn_num_cus());
-  if (a.S > 256) {
-    OP_ENSURE_LDS((attn_bwd_dkdv_pers_kernel<HAS_BIAS, HAS_PAD, 5, true>), (int)dkdv_pers_lds(257), "attn_bwd");
-    hipLaunchKernelGGL((attn_bwd_dkdv_pers_kernel<HAS_BIAS, HAS_PAD, 5, true>), dim3(nwg), dim3(PERS_NW * 64), sh, s, a, rows_pad, nitems);
-  } else {
-    OP_ENSURE_LDS((attn_bwd_dkdv_pers_kernel<HAS_BIAS, HAS_PAD, 4, false>), (int)dkdv_pers_lds(256), "attn_bwd");
-    hipLaunchKernelGGL((attn_bwd_dkdv_pers_kernel<HAS_BIAS, HAS_PAD, 4, false>), dim3(nwg), dim3(PERS_NW * 64), sh, s, a, rows_pad, nitems);
-  }
-  return OP_OK;
-}
 
 }  // namespace
 
 extern "C" int op_prof_begin(int family, double work, void* stream);
 extern "C" void op_prof_end(int slot, void* stream);
+
+// The tail of every profiled launch: closes the mark `slot`, then the status of the launch code (rc) or of the launch itself.
+static int attn_launched(int rc, int slot, void* stream) {
+  op_prof_end(slot, stream);
+  if (rc != OP_OK) return rc;
+  OP_LAUNCH_CHECK();
+  return OP_OK;
+}
 
 extern "C" {
 
@@ -2892,9 +2857,9 @@ extern "C" {
 // (the persistent dQ + dBias kernel of the 193 ... 257-token streams has its own chunk rule; which of the two kernels a call takes
 // also depends on arguments this query does not see -- the larger count is returned, slabs a kernel does not write stay zero)
 int64_t op_attn_bwd_dbias_slabs(int64_t B, int64_t S, int64_t heads, int64_t tune) {
-  if ((tune & 1) || ceil_div(S, BKV) > 6) return ceil_div(B, sep_bchunk(B, S, heads));  // the separate dBias kernel: a slab per chunk
-  const int64_t n = dbias_chunks(B, S, heads, !(tune & 1), (tune & 2) != 0, (int)((tune >> 4) & 63));
-  if (!(tune & 1) && !(tune & 1024) && pers_bwd_shape(S)) return max(n, (int64_t)pers_bwd_chunks(B, S, heads));
+  if ((tune & BWD_SEPARATE_DBIAS) || ceil_div(S, BKV) > 6) return ceil_div(B, sep_bchunk(B, S, heads));  // the separate dBias kernel: a slab per chunk
+  const int64_t n = dbias_chunks(B, S, heads, true, (tune & BWD_ROUND2_CHUNKS) != 0, (int)((tune >> BWD_CHUNKS_SHIFT) & BWD_CHUNKS_MASK));
+  if (!(tune & BWD_NO_PERS_DQ) && pers_bwd_shape(S)) return max(n, (int64_t)pers_bwd_chunks(B, S, heads));
   return n;
 }
 
@@ -2920,52 +2885,43 @@ int op_attn_fwd(const void* q, const void* k, const void* v, int64_t ld, const v
   hipStream_t s = (hipStream_t)stream;
   // resident-K/V kernel: needs the fragment-major bias image when a bias is used, and 1/scale exact in bf16 (head_dim 64)
   const bool inv_exact = (float)(bf16_t)(1.0f / scale) * scale == 1.0f;
+  const bf16_t* fr = (const bf16_t*)bias_frag;
   // persistent kernel (round 4): 193 ... 256 tokens (<= 16 query blocks = one per wave) or exactly 257 (256 + a lone query); tune bit 7: off
-  if (!(tune & 1) && !(tune & 128) && S > 192 && S <= 257 && (!bias || (bias_frag && inv_exact))) {
+  if (!(tune & FWD_STREAMING) && !(tune & FWD_NO_PERS) && S > 192 && S <= 257 && (!bias || (bias_frag && inv_exact))) {
     const int rows_pad = ceil_div(S, 32) * 32;
     const size_t sh = (size_t)4 * rows_pad * 128 + 2 * PERS_NW * PERS_SCR * 4;
     const int nitems = (int)(B * heads);
-    const int nwg = min(nitems, attn_num_cus());
-    const bf16_t* fr = (const bf16_t*)bias_frag;
-    int rc;
-    if (bias && key_pad) rc = launch_fwd_pers<true, true>(a, fr, nwg, sh, rows_pad, nitems, s);
-    else if (bias) rc = launch_fwd_pers<true, false>(a, fr, nwg, sh, rows_pad, nitems, s);
-    else if (key_pad) rc = launch_fwd_pers<false, true>(a, fr, nwg, sh, rows_pad, nitems, s);
-    else rc = launch_fwd_pers<false, false>(a, fr, nwg, sh, rows_pad, nitems, s);
-    op_prof_end(slot, stream);
-    if (rc != OP_OK) return rc;
-    OP_LAUNCH_CHECK();
-    return OP_OK;
+    const int nwg = min(nitems, op_num_cus());
+    return attn_launched(with_bias_pad(bias, key_pad, [&](auto hb, auto hp) {
+      constexpr auto kern = attn_fwd_pers_kernel<decltype(hb)::value, decltype(hp)::value>;
+      OP_ENSURE_LDS(kern, 4 * PERS_MAX_ROWS * 128 + 2 * PERS_NW * PERS_SCR * 4, "attn_fwd");
+      hipLaunchKernelGGL(kern, dim3(nwg), dim3(PERS_NW * 64), sh, s, a, fr, rows_pad, nitems);
+      return OP_OK;
+    }), slot, stream);
   }
-  if (!(tune & 1) && S <= RES_MAX_S && (!bias || (bias_frag && inv_exact))) {
+  if (!(tune & FWD_STREAMING) && S <= RES_MAX_S && (!bias || (bias_frag && inv_exact))) {
     const int nqb = ceil_div(S, 16);
     const int nwg = ceil_div(nqb, RES_MAX_NW);
     const int qb_per_wg = ceil_div(nqb, nwg);              // 16-query blocks per workgroup
     int nwaves = qb_per_wg;                                  // waves per workgroup (a wave takes blocks wid, wid + nwaves, ...)
-    if ((tune >> 3) & 15) nwaves = min(qb_per_wg, (int)((tune >> 3) & 15));   // (tests / A-B timing)
+    const int forced_waves = (int)((tune >> FWD_WAVES_SHIFT) & FWD_WAVES_MASK);
+    if (forced_waves) nwaves = min(qb_per_wg, forced_waves);  // (tests / A-B timing)
     else if (qb_per_wg == 9) nwaves = 8;                     // S = 257 ... 272: see the kernel
     const int rows_pad = ceil_div(S, 32) * 32;
     const size_t sh = (size_t)2 * rows_pad * 128;
     const dim3 rgrid(nwg, (unsigned)heads, (unsigned)B);
-    const int abl = (int)((tune >> 1) & 3);
-    const bf16_t* fr = (const bf16_t*)bias_frag;
-    int rc;
-    if (bias && key_pad) rc = launch_fwd_res<true, true>(a, fr, rgrid, nwaves, sh, rows_pad, qb_per_wg, abl, s);
-    else if (bias) rc = launch_fwd_res<true, false>(a, fr, rgrid, nwaves, sh, rows_pad, qb_per_wg, abl, s);
-    else if (key_pad) rc = launch_fwd_res<false, true>(a, fr, rgrid, nwaves, sh, rows_pad, qb_per_wg, abl, s);
-    else rc = launch_fwd_res<false, false>(a, fr, rgrid, nwaves, sh, rows_pad, qb_per_wg, abl, s);
-    op_prof_end(slot, stream);
-    if (rc != OP_OK) return rc;
-    OP_LAUNCH_CHECK();
-    return OP_OK;
+    const int abl = (int)((tune >> FWD_ABLATE_SHIFT) & FWD_ABLATE_MASK);
+    return attn_launched(with_bias_pad(bias, key_pad, [&](auto hb, auto hp) {
+      constexpr auto kern = attn_fwd_res_kernel<decltype(hb)::value, decltype(hp)::value>;
+      OP_ENSURE_LDS(kern, 2 * RES_MAX_S * 128, "attn_fwd");
+      hipLaunchKernelGGL(kern, rgrid, dim3(nwaves * 64), sh, s, a, fr, rows_pad, qb_per_wg, abl);
+      return OP_OK;
+    }), slot, stream);
   }
-  if (bias && key_pad) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, dim3(256), 0, s, a);
-  else if (bias) hipLaunchKernelGGL((attn_fwd_kernel<true, false>), grid, dim3(256), 0, s, a);
-  else if (key_pad) hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((attn_fwd_kernel<false, false>), grid, dim3(256), 0, s, a);
-  op_prof_end(slot, stream);
-  OP_LAUNCH_CHECK();
-  return OP_OK;
+  return attn_launched(with_bias_pad(bias, key_pad, [&](auto hb, auto hp) {
+    hipLaunchKernelGGL((attn_fwd_kernel<decltype(hb)::value, decltype(hp)::value>), grid, dim3(256), 0, s, a);
+    return OP_OK;
+  }), slot, stream);
 }
 
 
@@ -3010,9 +2966,10 @@ int op_attn_bwd(const void* q, const void* k, const void* v, int64_t ld, const v
                 float* delta, void* dq,
                 void* dk, void* dv, int64_t ldg, float* dbias, int64_t B, int64_t S, int64_t Spad, int64_t heads,
                 int64_t head_dim, float scale, int64_t tune, void* stream) {
-  const bool merge_dbias = !(tune & 1);
+  const bool merge_dbias = !(tune & BWD_SEPARATE_DBIAS);
   OP_CHECK_ARG(q && k && v && dout && lse && delta && dq && dk && dv, "attn_bwd: null pointer");
   OP_CHECK_ARG(head_dim == HD, "attn_bwd: head_dim %lld unsupported (only 64)", (long long)head_dim);
+  OP_CHECK_ARG(B > 0 && S > 0 && heads > 0, "attn_bwd: bad sizes");
   OP_CHECK_ARG(Spad >= ((S + 127) / 128) * 128 && Spad % 8 == 0, "attn_bwd: Spad must be >= S rounded up to 128");
   OP_CHECK_ARG((bias == nullptr) == (biasT == nullptr), "attn_bwd: bias and biasT must be given together");
   OP_CHECK_ARG(!dbias || bias, "attn_bwd: dbias without a bias");
@@ -3025,11 +2982,10 @@ int op_attn_bwd(const void* q, const void* k, const void* v, int64_t ld, const v
   a.key_pad = (const uint8_t*)key_pad; a.lse = lse; a.delta = delta; a.out = (const bf16_t*)out; a.delta_w = delta;
   a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.ldg = ldg; a.dbias = dbias;
   a.B = (int)B; a.S = (int)S; a.Spad = (int)Spad; a.heads = (int)heads; a.scale = scale;
-  a.lone_keys = !(tune & 2048);
+  a.lone_keys = !(tune & BWD_NO_LONE_KEYS);
   a.bchunk = sep_bchunk(B, S, heads);
   hipStream_t s = (hipStream_t)stream;
   const double fl = 4.0 * (double)B * (double)heads * (double)S * (double)S * HD;
-  int slot;
   const int bchunk_dkdv = a.bchunk;
   auto launch_dkdv = [&]() {
     AttnBwdArgs d = a;
@@ -3039,24 +2995,24 @@ int op_attn_bwd(const void* q, const void* k, const void* v, int64_t ld, const v
     // third less padding at S = 257).  Measured (tools/attn_dkdv_ab.py, backward + dBias, B = 128): S = 257 0.6708 vs 0.6733 ms,
     // S = 250 0.5179 vs 0.5467, S = 65 0.1233 vs 0.1445, S = 785 1.436 vs 1.470 -- the narrower wave reads every Q / dO fragment
     // for half as many MFMAs; 128 stays.  tune bits 2-3: 2 forces 64 (A/B timing).
-    const bool kb1 = ((tune >> 2) & 3) == 2;
-    if (kb1) {
-      if (bias) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, 1>), dim3(ceil_div(S, 64), (unsigned)heads, (unsigned)B), dim3(256), 0, s, d);
-      else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, 1>), dim3(ceil_div(S, 64), (unsigned)heads, (unsigned)B), dim3(256), 0, s, d);
-    } else {
-      if (bias) hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, 2>), dim3(ceil_div(S, 128), (unsigned)heads, (unsigned)B), dim3(256), 0, s, d);
-      else hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, 2>), dim3(ceil_div(S, 128), (unsigned)heads, (unsigned)B), dim3(256), 0, s, d);
-    }
-    op_prof_end(sl, stream);
+    const int kb = ((tune >> BWD_DKDV_KEYS_SHIFT) & BWD_DKDV_KEYS_MASK) == 2 ? 1 : 2;
+    return attn_launched(op_with_bool(bias != nullptr, [&](auto hb) {
+      return op_with_int<1, 2>(kb, [&](auto kbc) {
+        constexpr int KB = decltype(kbc)::value;
+        hipLaunchKernelGGL((attn_bwd_dkdv_kernel<decltype(hb)::value, KB>), dim3(ceil_div(S, 64 * KB), (unsigned)heads, (unsigned)B), dim3(256),
+                           0, s, d);
+        return OP_OK;
+      });
+    }), sl, stream);
   };
   if (!out) {  // delta precomputed (op_attn_bwd_delta): the kernels are independent
-    launch_dkdv();
-    OP_LAUNCH_CHECK();
+    const int rc = launch_dkdv();
+    if (rc != OP_OK) return rc;
   }
   const int nt = ceil_div(S, BKV);
   // persistent dQ (+ dBias) kernel (round 4): 193 ... 257 tokens, shared bias image in fragment-major form (or no bias), delta computed
   // in the kernel (out given); tune bit 10: off
-  if (merge_dbias && !(tune & 1024) && out && pers_bwd_shape(S) && a.bias_bs == 0 &&
+  if (merge_dbias && !(tune & BWD_NO_PERS_DQ) && out && pers_bwd_shape(S) && a.bias_bs == 0 &&
       (!bias || (a.bias_frag != nullptr && (float)(bf16_t)(1.0f / scale) * scale == 1.0f))) {
     const int nqb = ceil_div(S, 16);
     const int nqh = ceil_div(min(nqb, 2 * PERS_NW), PERS_NW);
@@ -3067,74 +3023,62 @@ int op_attn_bwd(const void* q, const void* k, const void* v, int64_t ld, const v
     const int nwg = chunks * (int)heads * nqh;
     AttnBwdArgs d = a;
     if (!bias) d.dbias = nullptr;
-    slot = op_prof_begin(2, 1.5 * fl, stream);
-    int rc;
-    if (bias && key_pad) rc = launch_bwd_dq_pers<true, true>(d, nwg, sh, rows_pad, nqh, s);
-    else if (bias) rc = launch_bwd_dq_pers<true, false>(d, nwg, sh, rows_pad, nqh, s);
-    else if (key_pad) rc = launch_bwd_dq_pers<false, true>(d, nwg, sh, rows_pad, nqh, s);
-    else rc = launch_bwd_dq_pers<false, false>(d, nwg, sh, rows_pad, nqh, s);
-    op_prof_end(slot, stream);
+    const int slot = op_prof_begin(2, 1.5 * fl, stream);
+    int rc = attn_launched(with_bias_pad(bias, key_pad, [&](auto hb, auto hp) {
+      return op_with_bool(S > 256, [&](auto lone) {  // 257 = 256 + a lone token: a fifth key tile of one 16-key block
+        constexpr bool LONE = decltype(lone)::value;
+        constexpr auto kern = attn_bwd_dq_pers_kernel<decltype(hb)::value, decltype(hp)::value, LONE ? 5 : 4, LONE ? 1 : 4>;
+        OP_ENSURE_LDS(kern, 4 * PERS_MAX_ROWS * 128 + 2 * PERS_NW * 64 * 4, "attn_bwd");
+        hipLaunchKernelGGL(kern, dim3(nwg), dim3(PERS_NW * 64), sh, s, d, rows_pad, nqh);
+        return OP_OK;
+      });
+    }), slot, stream);
     if (rc != OP_OK) return rc;
-    OP_LAUNCH_CHECK();
     a.bchunk = bchunk_dkdv;
-    // persistent dK / dV kernel (round 4; tune bit 12: the rounds 1-3 kernel).  Measured at B = 128 (tools/attn_pers_ab.py): S = 257
-    // -12 % on the backward pair, S = 250 -2 %, S = 197 -1 %, S = 256 +5 % (two full key workgroups: nothing to gain) -- bit 13 forces it
-    if (!(tune & 4096) && (!bias || biasT) && (S != 256 || (tune & 8192))) {
-      const int sl = op_prof_begin(2, 2.0 * fl, stream);
-      if (bias && key_pad) rc = launch_bwd_dkdv_pers<true, true>(a, s);
-      else if (bias) rc = launch_bwd_dkdv_pers<true, false>(a, s);
-      else if (key_pad) rc = launch_bwd_dkdv_pers<false, true>(a, s);
-      else rc = launch_bwd_dkdv_pers<false, false>(a, s);
-      op_prof_end(sl, stream);
-      if (rc != OP_OK) return rc;
-    } else {
-      launch_dkdv();
-    }
-    OP_LAUNCH_CHECK();
-    return OP_OK;
+    // persistent dK / dV kernel (round 4; tune bit 12: the rounds 1-3 kernel): one workgroup per CU walks the (sample, head) items.
+    // Measured at B = 128 (tools/attn_pers_ab.py): S = 257 -12 % on the backward pair, S = 250 -2 %, S = 197 -1 %, S = 256 +5 % (two
+    // full key workgroups: nothing to gain) -- bit 13 forces it
+    if ((tune & BWD_NO_PERS_DKDV) || (bias && !biasT) || (S == 256 && !(tune & BWD_PERS_DKDV_256))) return launch_dkdv();
+    const int dk_rows = dkdv_pers_rows(S), nitems = a.B * a.heads, dk_nwg = min(nitems, op_num_cus());
+    const int dk_slot = op_prof_begin(2, 2.0 * fl, stream);
+    return attn_launched(with_bias_pad(bias, key_pad, [&](auto hb, auto hp) {
+      return op_with_bool(S > 256, [&](auto lone) {
+        constexpr bool LONE = decltype(lone)::value;
+        constexpr auto kern = attn_bwd_dkdv_pers_kernel<decltype(hb)::value, decltype(hp)::value, LONE ? 5 : 4, LONE>;
+        OP_ENSURE_LDS(kern, (int)dkdv_pers_lds(LONE ? 257 : 256), "attn_bwd");
+        hipLaunchKernelGGL(kern, dim3(dk_nwg), dim3(PERS_NW * 64), dkdv_pers_lds(S), s, a, dk_rows, nitems);
+        return OP_OK;
+      });
+    }), dk_slot, stream);
   }
   if (dbias && nt <= 6 && merge_dbias) {  // dQ and dBias together: dS summed over the batch chunk in registers
     // per-sample bias: every sample is its own chunk, slab b of dbias is the gradient of sample b's bias image
-    const int chunks = a.bias_bs != 0 ? (int)B : dbias_chunks(B, S, heads, true, (tune & 2) != 0, (int)((tune >> 4) & 63));
+    const int chunks = a.bias_bs != 0 ? (int)B : dbias_chunks(B, S, heads, true, (tune & BWD_ROUND2_CHUNKS) != 0,
+                                                              (int)((tune >> BWD_CHUNKS_SHIFT) & BWD_CHUNKS_MASK));
     a.bchunk = ceil_div(B, chunks);
     const dim3 grid(ceil_div(S, 64), (unsigned)heads, (unsigned)chunks);
     const bool one_block = ceil_div(S - (nt - 1) * BKV, 16) == 1;  // last key tile = a single 16-key block (S = 257: 256 + CLS)
     // (the fragment path of 5 full tiles / 6 tiles would spill its dS accumulators: those lengths keep the round-1 softmax code)
     const bool frag = a.bias_frag != nullptr && (float)(bf16_t)(1.0f / scale) * scale == 1.0f && (nt <= 4 || (nt == 5 && one_block));
-#define DQDB(N)                                                                                                           \
-  do {                                                                                                                    \
-    if (frag && one_block) hipLaunchKernelGGL((attn_bwd_dq_dbias_kernel<N, true, 1>), grid, dim3(256), 0, s, a);           \
-    else if (frag) hipLaunchKernelGGL((attn_bwd_dq_dbias_kernel<N, true, 4>), grid, dim3(256), 0, s, a);                   \
-    else if (one_block) hipLaunchKernelGGL((attn_bwd_dq_dbias_kernel<N, false, 1>), grid, dim3(256), 0, s, a);             \
-    else hipLaunchKernelGGL((attn_bwd_dq_dbias_kernel<N, false, 4>), grid, dim3(256), 0, s, a);                            \
-  } while (0)
-    slot = op_prof_begin(2, 1.5 * fl, stream);
-    switch (nt) {
-      case 1: DQDB(1); break;
-      case 2: DQDB(2); break;
-      case 3: DQDB(3); break;
-      case 4: DQDB(4); break;
-      case 5: DQDB(5); break;
-      default: DQDB(6); break;
-    }
-#undef DQDB
-    op_prof_end(slot, stream);
-    OP_LAUNCH_CHECK();
-    if (out) {
-      launch_dkdv();
-      OP_LAUNCH_CHECK();
-    }
+    const int slot = op_prof_begin(2, 1.5 * fl, stream);
+    const int rc = attn_launched(op_with_int<1, 2, 3, 4, 5, 6>(nt, [&](auto n) {
+      return op_with_bool(frag, [&](auto fr) {
+        return op_with_bool(one_block, [&](auto ob) {
+          hipLaunchKernelGGL((attn_bwd_dq_dbias_kernel<decltype(n)::value, decltype(fr)::value, decltype(ob)::value ? 1 : 4>), grid, dim3(256),
+                             0, s, a);
+          return OP_OK;
+        });
+      });
+    }), slot, stream);
+    return rc != OP_OK || !out ? rc : launch_dkdv();
+  }
+  const int slot = op_prof_begin(2, 1.5 * fl, stream);
+  int rc = attn_launched(op_with_bool(bias != nullptr, [&](auto hb) {
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<decltype(hb)::value>, dim3(ceil_div(S, BQ), (unsigned)heads, (unsigned)B), dim3(256), 0, s, a);
     return OP_OK;
-  }
-  slot = op_prof_begin(2, 1.5 * fl, stream);
-  if (bias) hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, dim3(ceil_div(S, BQ), (unsigned)heads, (unsigned)B), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, dim3(ceil_div(S, BQ), (unsigned)heads, (unsigned)B), dim3(256), 0, s, a);
-  op_prof_end(slot, stream);
-  OP_LAUNCH_CHECK();
-  if (out) {
-    launch_dkdv();
-    OP_LAUNCH_CHECK();
-  }
+  }), slot, stream);
+  if (rc == OP_OK && out) rc = launch_dkdv();
+  if (rc != OP_OK) return rc;
   if (dbias) {
     if (a.bias_bs != 0) a.bchunk = 1;  // per-sample bias images: one sample per workgroup, slab b of dbias for sample b
     const int chunks = ceil_div(B, a.bchunk);

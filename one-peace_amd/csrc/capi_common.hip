@@ -19,6 +19,19 @@ extern "C" const char* op_last_error(void) { return g_err; }
 
 extern "C" int op_abi_version(void) { return 10; }
 
+// CUs of the CURRENT device, cached per device (a process may drive several)
+int op_num_cus() {
+  static int cached[16] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+  if (cached[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cached[dev] = n;
+  }
+  return cached[dev];
+}
+
 // ---- live per-kernel-family timing with HIP events on the launch stream ---------------------------
 // bench.py enables this around its timed region; gemm launches then record an event pair on the
 // stream they are enqueued on.  Disabled (the default) it costs one relaxed load per launch.

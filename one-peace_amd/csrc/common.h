@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 typedef __bf16 bf16_t;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -55,6 +56,20 @@ extern "C" void op_set_error(const char* fmt, ...);
       return (int)e__;                                                     \
     }                                                                      \
   } while (0)
+
+// ---- a runtime value selects a template instantiation (host) -------------------------------------
+// f is a generic lambda that gets the value as a std::integral_constant and returns the op's int status; nest the calls for several
+// values.  OP_CHECK_ARG / OP_ENSURE_LDS / OP_LAUNCH_CHECK work inside f (their statics are per instantiation of its body).
+template <typename F> inline int op_with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+template <int... Vs, typename F> inline int op_with_int(int v, F&& f, int otherwise = OP_ENOTSUP) {  // f(V) for the V that equals v
+  int rc = otherwise;
+  (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return rc;
+}
+template <bool BF16> using op_elem_t = std::conditional_t<BF16, bf16_t, float>;  // op_with_bool(dtype == OP_DT_BF16, ...)
+
+// compute units of the current device (cached per device; 256 when the query fails)
+int op_num_cus();
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -2115,16 +2115,8 @@ int launch256v(const GemmArgs& a, hipStream_t s, dim3 grid, size_t sh) {
 
 // persistent grouped kernel: one workgroup per CU (or per tile when there are fewer tiles)
 static int num_cus() {
-  static int cached[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-  if (cached[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cached[dev] = n - n % 8;  // a multiple of the 8 XCDs: workgroup w stays on XCD w % 8 over its whole tile list
-    if (cached[dev] <= 0) cached[dev] = 8;
-  }
-  return cached[dev];
+  const int n = op_num_cus() / 8 * 8;  // a multiple of the 8 XCDs: workgroup w stays on XCD w % 8 over its whole tile list
+  return n > 0 ? n : 8;
 }
 
 template <int EPI>
@@ -2138,10 +2130,7 @@ int launch256p(const GroupArgs& ga, hipStream_t s, bool persistent = true) {
 }
 
 static int launch256p_any(const GroupArgs& ga, int epi, hipStream_t s, bool persistent) {
-  if (epi == EPI_BIAS) return launch256p<EPI_BIAS>(ga, s, persistent);
-  if (epi == EPI_RESID) return launch256p<EPI_RESID>(ga, s, persistent);
-  if (epi == EPI_RESID_ROWS) return launch256p<EPI_RESID_ROWS>(ga, s, persistent);
-  return OP_ENOTSUP;
+  return op_with_int<EPI_BIAS, EPI_RESID, EPI_RESID_ROWS>(epi, [&](auto e) { return launch256p<decltype(e)::value>(ga, s, persistent); });
 }
 
 // single-problem GroupArgs of a plain launch
@@ -2214,14 +2203,18 @@ template <int EPI>
 int launch(const GemmArgs& a, int glds, hipStream_t s, int splits = 1, int batch = 1, NtBatch bt = NtBatch{0, 0, 0, 0}) {
   const dim3 grid(a.tiles_m * a.tiles_n, splits, batch);
   const size_t sh = 4 * TILE_BYTES;
-  if (glds) OP_ENSURE_LDS((gemm_nt_kernel<EPI, true>), sh, "gemm");
-  else OP_ENSURE_LDS((gemm_nt_kernel<EPI, false>), sh, "gemm");
-  if (glds)
-    hipLaunchKernelGGL((gemm_nt_kernel<EPI, true>), grid, dim3(256), sh, s, a, bt);
-  else
-    hipLaunchKernelGGL((gemm_nt_kernel<EPI, false>), grid, dim3(256), sh, s, a, bt);
-  OP_LAUNCH_CHECK();
-  return OP_OK;
+  return op_with_bool(glds != 0, [&](auto g) {
+    constexpr auto kern = gemm_nt_kernel<EPI, decltype(g)::value>;
+    OP_ENSURE_LDS(kern, sh, "gemm");
+    hipLaunchKernelGGL(kern, grid, dim3(256), sh, s, a, bt);
+    OP_LAUNCH_CHECK();
+    return OP_OK;
+  });
+}
+
+// f(EPI) for the epilogue of an NT launch (gemm_nt_impl has checked the range)
+template <typename F> int with_epilogue(int epi, F&& f) {
+  return op_with_int<EPI_BIAS, EPI_F32, EPI_GEGLU, EPI_RESID, EPI_RESID_ROWS>(epi, f);
 }
 
 
@@ -2514,21 +2507,9 @@ static int gemm_nt_impl(const void* A, int64_t lda, const void* B0, const void* 
     // L2 tile-group depth (tools/gemm_gm.py): few column tiles (N = 1536) -> walk all N-tiles of ONE M-tile together
     // (+3-5 %); wide outputs -> 8 M-tiles per group (+1-2 % over 4)
     a.gm = T.gm > 0 ? T.gm : (a.tiles_n <= 8 ? 1 : 8);
-    switch (epi) {
-      case EPI_BIAS: rc = launch256<EPI_BIAS>(a, s, T, plan.splits); break;
-      case EPI_F32: rc = launch256<EPI_F32>(a, s, T, plan.splits); break;
-      case EPI_GEGLU: rc = launch256<EPI_GEGLU>(a, s, T, plan.splits); break;
-      case EPI_RESID_ROWS: rc = launch256<EPI_RESID_ROWS>(a, s, T, plan.splits); break;
-      default: rc = launch256<EPI_RESID>(a, s, T, plan.splits); break;
-    }
+    rc = with_epilogue(epi, [&](auto e) { return launch256<decltype(e)::value>(a, s, T, plan.splits); });
   } else {
-    switch (epi) {
-      case EPI_BIAS: rc = launch<EPI_BIAS>(a, T.glds, s, plan.splits); break;
-      case EPI_F32: rc = launch<EPI_F32>(a, T.glds, s, plan.splits); break;
-      case EPI_GEGLU: rc = launch<EPI_GEGLU>(a, T.glds, s, plan.splits); break;
-      case EPI_RESID_ROWS: rc = launch<EPI_RESID_ROWS>(a, T.glds, s, plan.splits); break;
-      default: rc = launch<EPI_RESID>(a, T.glds, s, plan.splits); break;
-    }
+    rc = with_epilogue(epi, [&](auto e) { return launch<decltype(e)::value>(a, T.glds, s, plan.splits); });
   }
   if (rc == OP_OK && plan.splits > 1) {
     int64_t nb = ((int64_t)M * (N / 8) + 255) / 256;
@@ -2802,6 +2783,28 @@ static int tn_build_schedule(TnGroupArgs& ga, int nwg, bool solo) {
   }
 }
 
+// The part of a grouped launch that the problem sizes decide: order[] = the caller's indices, longest K first (stable insertion sort:
+// greedy list scheduling wants the long tiles early, equal K keep the caller's order), ga.pr[i].tiles_m / tiles_n / K in that order,
+// and the queues for `nwg` workgroups (<= 0: one per CU; at most one per tile).  Returns the number of workgroups.
+static int tn_plan_queues(TnGroupArgs& ga, int nprob, const int64_t* M, const int64_t* N, const int64_t* K, int nwg, int64_t tune, int* order) {
+  for (int i = 0; i < nprob; ++i) order[i] = i;
+  for (int i = 1; i < nprob; ++i)
+    for (int j = i; j > 0 && K[order[j]] > K[order[j - 1]]; --j) { const int tmp = order[j]; order[j] = order[j - 1]; order[j - 1] = tmp; }
+  memset(&ga, 0, sizeof(ga));
+  ga.nprob = nprob;
+  int64_t tiles = 0;
+  for (int i = 0; i < nprob; ++i) {
+    ga.pr[i].tiles_m = ceil_div(M[order[i]], 256);
+    ga.pr[i].tiles_n = ceil_div(N[order[i]], 256);
+    ga.pr[i].K = (int)K[order[i]];
+    tiles += (int64_t)ga.pr[i].tiles_m * ga.pr[i].tiles_n;
+  }
+  if (nwg <= 0) nwg = num_cus();
+  if (nwg > tiles) nwg = (int)tiles;
+  tn_build_schedule(ga, nwg, ((tune >> 10) & 1) != 0);
+  return nwg;
+}
+
 // Bytes of the counter block op_gemm_tn_grouped needs: device memory the caller zeroes ONCE; every launch leaves it zeroed.
 // One block per stream that may run the op (launches on one stream are ordered, the block is re-armed by the launch itself).
 int64_t op_gemm_tn_grouped_counter_bytes(void) { return (int64_t)(9 * TN_CTR_STRIDE) * 8; }
@@ -2814,22 +2817,8 @@ int64_t op_gemm_tn_grouped_plan(int64_t nprob, const int64_t* M, const int64_t* 
                                 int32_t* out, int64_t cap) {
   if (nprob < 1 || nprob > TN_MAX_PROB || !M || !N || !K || !out) return OP_EINVAL;
   int order[TN_MAX_PROB];
-  for (int i = 0; i < (int)nprob; ++i) order[i] = i;
-  for (int i = 1; i < (int)nprob; ++i)
-    for (int j = i; j > 0 && K[order[j]] > K[order[j - 1]]; --j) { const int tmp = order[j]; order[j] = order[j - 1]; order[j - 1] = tmp; }
   TnGroupArgs ga;
-  memset(&ga, 0, sizeof(ga));
-  ga.nprob = (int)nprob;
-  int64_t tiles = 0;
-  for (int i = 0; i < (int)nprob; ++i) {
-    ga.pr[i].tiles_m = ceil_div(M[order[i]], 256);
-    ga.pr[i].tiles_n = ceil_div(N[order[i]], 256);
-    ga.pr[i].K = (int)K[order[i]];
-    tiles += (int64_t)ga.pr[i].tiles_m * ga.pr[i].tiles_n;
-  }
-  int nwg = workgroups > 0 ? (int)workgroups : num_cus();
-  if (nwg > tiles) nwg = (int)tiles;
-  tn_build_schedule(ga, nwg, ((tune >> 10) & 1) != 0);
+  tn_plan_queues(ga, (int)nprob, M, N, K, workgroups > 0 ? (int)workgroups : 0, tune, order);
   int64_t n = 0;
   for (int x = 0; x < 8; ++x) {
     const int len = tn_queue_len(ga, x);
@@ -2868,23 +2857,17 @@ int op_gemm_tn_grouped_lists(int64_t nprob, const void* const* A, const int64_t*
                    (long long)N[i], (long long)K[i]);
       return OP_ENOTSUP;
     }
-    order[i] = i;
   }
-  for (int i = 1; i < (int)nprob; ++i)  // longest K first (stable insertion sort): greedy list scheduling wants the long tiles early
-    for (int j = i; j > 0 && K[order[j]] > K[order[j - 1]]; --j) { const int tmp = order[j]; order[j] = order[j - 1]; order[j - 1] = tmp; }
   TnGroupArgs ga;
-  memset(&ga, 0, sizeof(ga));
-  ga.nprob = (int)nprob;
+  const int nwg = tn_plan_queues(ga, (int)nprob, M, N, K, (int)(tune & 1023), tune, order);
   ga.ctr = (unsigned long long*)counters;
   double work = 0.0;
-  int64_t tiles = 0;
   for (int i = 0; i < (int)nprob; ++i) {
     const int s = order[i];
     TnProb& q = ga.pr[i];
     q.A = (const bf16_t*)A[s]; q.B = (const bf16_t*)B[s]; q.C = (bf16_t*)C[s];
     q.lda = lda[s]; q.ldb = ldb[s]; q.ldc = ldc[s];
-    q.M = (int)M[s]; q.N = (int)N[s]; q.K = (int)K[s];
-    q.tiles_m = ceil_div(M[s], 256); q.tiles_n = ceil_div(N[s], 256);
+    q.M = (int)M[s]; q.N = (int)N[s];
     q.accumulate = accumulate[s] != 0;
     if (rowdot != nullptr && rowdot[s] != nullptr) {  // (the side product rides on the full-tile accumulate epilogue)
       OP_CHECK_ARG(W != nullptr && ldw != nullptr && W[s] != nullptr && q.accumulate && M[s] % 256 == 0 && N[s] % 256 == 0 && ldw[s] % 8 == 0 &&
@@ -2899,13 +2882,8 @@ int op_gemm_tn_grouped_lists(int64_t nprob, const void* const* A, const int64_t*
       OP_CHECK_ARG(n_ktiles != nullptr && n_ktiles[s] != nullptr, "gemm_tn_grouped: problem %d has a K-tile list without its count", s);
       q.ktiles = ktiles[s]; q.n_ktiles = n_ktiles[s];
     }
-    tiles += (int64_t)q.tiles_m * q.tiles_n;
     work += 2.0 * (double)M[s] * (double)N[s] * (double)K[s];
   }
-  int nwg = (int)(tune & 1023);
-  if (nwg <= 0) nwg = num_cus();
-  if (nwg > tiles) nwg = (int)tiles;
-  tn_build_schedule(ga, nwg, ((tune >> 10) & 1) != 0);
   const size_t sh = STAGES2 * STAGE2_BYTES;
   OP_ENSURE_LDS(gemm256w_tn_grouped_kernel, (int)sh, "gemm_tn_grouped");
   const int slot = op_prof_begin(0, work, stream);

@@ -595,29 +595,64 @@ inline int ln_grid(int64_t rows, int nw, int cap) {
   return (int)blocks;
 }
 
-template <typename T, bool GELU>
-int ln_fwd_dispatch(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd, int64_t rows,
-                    int cols, float eps, hipStream_t s, const int* xmap = nullptr) {
-  const T* X = (const T*)x; const T* W = (const T*)w; const T* B = (const T*)b; T* Y = (T*)y;
-  // cache policy: non-temporal row accesses for a TRAINING pass (the caller wants the statistics: a backward follows) over a matrix of
-  // >= 64 MiB -- it streams once, and what it left in L2 / Infinity Cache only displaced the next GEMM's panels (-2 % on the headline
-  // step with the hint on every row-wise kernel); inference keeps the default policy: there the consumer finds the row matrix in the
-  // caches (+1 ... 5 % with the hint at the image tower's sizes; profiles/r4_nontemporal_ab.txt)
-  const bool nt = mean != nullptr && (int64_t)rows * cols * (int64_t)sizeof(T) >= ((int64_t)64 << 20);
-#define LN_F(CH, NW)                                                                                                                      \
-  do {                                                                                                                                    \
-    if (nt) hipLaunchKernelGGL((ln_fwd_kernel<T, CH, NW, GELU, true>), dim3(ln_grid(rows, NW, g_ln_blocks_fwd)), dim3(256), 0, s, X, W, B, Y, mean, rstd, rows, cols, eps, (uint8_t*)nullptr, (float*)nullptr, xmap); \
-    else hipLaunchKernelGGL((ln_fwd_kernel<T, CH, NW, GELU, false>), dim3(ln_grid(rows, NW, g_ln_blocks_fwd)), dim3(256), 0, s, X, W, B, Y, mean, rstd, rows, cols, eps, (uint8_t*)nullptr, (float*)nullptr, xmap); \
-  } while (0)
-  if (cols <= 512) LN_F(1, 1);
-  else if (cols <= 1024) LN_F(2, 1);
-  else if (cols <= 1536) LN_F(3, 1);
-  else if (cols <= 2048) LN_F(4, 1);
-  else if (cols <= 4096) LN_F(2, 4);
-  else if (cols <= 6144) LN_F(3, 4);
-  else if (cols <= 8192) LN_F(4, 4);
-  else { op_set_error("layernorm: cols %d > 8192 unsupported", cols); return OP_ENOTSUP; }
-#undef LN_F
+// cols -> (CH 16-byte chunks per lane, NW waves per row): one wave per row up to 2048 columns, a 256-thread workgroup above; a row
+// holds at most 64 * NW * CH * 8 columns.  The ONLY place that knows the ladder (tests/ln_ref.py:ch_nw mirrors it).
+struct LnRoute { int max_cols, ch, nw; };
+constexpr LnRoute LN_ROUTES[] = {{512, 1, 1}, {1024, 2, 1}, {1536, 3, 1}, {2048, 4, 1}, {4096, 2, 4}, {6144, 3, 4}, {8192, 4, 4}};
+constexpr int ln_route(int cols) {  // index into LN_ROUTES, -1 above 8192
+  for (int i = 0; i < 7; ++i)
+    if (cols <= LN_ROUTES[i].max_cols) return i;
+  return -1;
+}
+constexpr bool ln_route_is(int cols, int ch, int nw) { return LN_ROUTES[ln_route(cols)].ch == ch && LN_ROUTES[ln_route(cols)].nw == nw; }
+static_assert(ln_route_is(8, 1, 1) && ln_route_is(512, 1, 1), "cols <= 512");
+static_assert(ln_route_is(520, 2, 1) && ln_route_is(1024, 2, 1), "cols <= 1024");
+static_assert(ln_route_is(1032, 3, 1) && ln_route_is(1536, 3, 1), "cols <= 1536");
+static_assert(ln_route_is(1544, 4, 1) && ln_route_is(2048, 4, 1), "cols <= 2048");
+static_assert(ln_route_is(2056, 2, 4) && ln_route_is(4096, 2, 4), "cols <= 4096");
+static_assert(ln_route_is(4104, 3, 4) && ln_route_is(6144, 3, 4), "cols <= 6144");
+static_assert(ln_route_is(6152, 4, 4) && ln_route_is(8192, 4, 4) && ln_route(8200) == -1, "cols <= 8192");
+
+// f(CH, NW) (as std::integral_constant) for the route of `cols`
+template <typename F> int ln_with_route(int cols, F&& f) {
+  const int r = ln_route(cols);
+  if (r < 0) { op_set_error("layernorm: cols %d > 8192 unsupported", cols); return OP_ENOTSUP; }
+  return op_with_int<0, 1, 2, 3, 4, 5, 6>(r, [&](auto i) {
+    return f(std::integral_constant<int, LN_ROUTES[decltype(i)::value].ch>{}, std::integral_constant<int, LN_ROUTES[decltype(i)::value].nw>{});
+  });
+}
+
+// cache policy: non-temporal row accesses for a TRAINING pass over a matrix of >= 64 MiB -- it streams once, and what it left in L2 /
+// Infinity Cache only displaced the next GEMM's panels (-2 % on the headline step with the hint on every row-wise kernel); inference
+// keeps the default policy: there the consumer finds the row matrix in the caches (+1 ... 5 % with the hint at the image tower's
+// sizes; profiles/r4_nontemporal_ab.txt)
+inline bool ln_streams(int64_t rows, int cols, size_t elem) { return rows * cols * (int64_t)elem >= ((int64_t)64 << 20); }
+
+// Q8 (bf16, no GELU, default cache policy: the only instantiations there are) also writes q8 / q8_scale
+template <typename T, bool GELU, bool Q8 = false>
+int ln_fwd_dispatch(const void* x, const void* w, const void* b, void* y, float* mean, float* rstd, int64_t rows, int cols, float eps,
+                    hipStream_t s, const int* xmap, void* q8 = nullptr, float* q8_scale = nullptr) {
+  // (a training pass is one whose caller wants the statistics: a backward follows)
+  const bool nt = !Q8 && mean != nullptr && ln_streams(rows, cols, sizeof(T));
+  return ln_with_route(cols, [&](auto ch, auto nw) {
+    constexpr int CH = decltype(ch)::value, NW = decltype(nw)::value;
+    auto launch = [&](auto ntc) {
+      hipLaunchKernelGGL((ln_fwd_kernel<T, CH, NW, GELU, decltype(ntc)::value, Q8>), dim3(ln_grid(rows, NW, g_ln_blocks_fwd)), dim3(256), 0,
+                         s, (const T*)x, (const T*)w, (const T*)b, (T*)y, mean, rstd, rows, cols, eps, (uint8_t*)q8, q8_scale, xmap);
+      OP_LAUNCH_CHECK();
+      return OP_OK;
+    };
+    if constexpr (Q8) return launch(std::false_type{});
+    else return op_with_bool(nt, launch);
+  });
+}
+
+// dw / db from the per-workgroup partials of a backward kernel ([grid][2][cols] fp32)
+template <typename T>
+int ln_reduce_dw_db(float* ws, void* dw, void* db, int grid, int cols, int accumulate, hipStream_t s) {
+  hipLaunchKernelGGL((partials_reduce3_kernel<T>), dim3(ceil_div(cols, 32), 2), dim3(256), 0, s, ws, ws + cols, (const float*)nullptr,
+                     (const bf16_t*)nullptr, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (T*)dw, (T*)db, (T*)nullptr, grid,
+                     (int64_t)2 * cols, cols, accumulate);
   OP_LAUNCH_CHECK();
   return OP_OK;
 }
@@ -625,38 +660,34 @@ int ln_fwd_dispatch(const void* x, const void* w, const void* b, void* y, float*
 template <typename T, bool GELU>
 int ln_bwd_dispatch(const void* dy, const void* x, const void* w, const void* b, const float* mean, const float* rstd,
                     const void* add, void* dx, void* dw, void* db, float* ws, int64_t rows, int cols, int accumulate,
-                    hipStream_t s, const int* xmap = nullptr) {
-  const T* DY = (const T*)dy; const T* X = (const T*)x; const T* W = (const T*)w; const T* B = (const T*)b; T* DX = (T*)dx;
-  const T* ADD = (const T*)add;
-  int grid = 0;
+                    hipStream_t s, const int* xmap) {
   float* wsk = (dw || db) ? ws : nullptr;
-  const bool nt = (int64_t)rows * cols * (int64_t)sizeof(T) >= ((int64_t)64 << 20);  // (see ln_fwd_dispatch)
-#define LN_B(CH, NW)                                                                                        \
-  do {                                                                                                      \
-    grid = ln_grid(rows, NW, g_ln_blocks_bwd);                                                                               \
-    size_t sh = (NW == 1) ? (size_t)4 * cols * sizeof(float) : 64;                                          \
-    if (nt) hipLaunchKernelGGL((ln_bwd_kernel<T, CH, NW, GELU, true>), dim3(grid), dim3(256), sh, s, DY, X, W, B, mean,   \
-                       rstd, ADD, DX, wsk, rows, cols, xmap);                                                    \
-    else hipLaunchKernelGGL((ln_bwd_kernel<T, CH, NW, GELU, false>), dim3(grid), dim3(256), sh, s, DY, X, W, B, mean,   \
-                       rstd, ADD, DX, wsk, rows, cols, xmap);                                                    \
-  } while (0)
-  if (cols <= 512) LN_B(1, 1);
-  else if (cols <= 1024) LN_B(2, 1);
-  else if (cols <= 1536) LN_B(3, 1);
-  else if (cols <= 2048) LN_B(4, 1);
-  else if (cols <= 4096) LN_B(2, 4);
-  else if (cols <= 6144) LN_B(3, 4);
-  else if (cols <= 8192) LN_B(4, 4);
-  else { op_set_error("layernorm: cols %d > 8192 unsupported", cols); return OP_ENOTSUP; }
-#undef LN_B
-  OP_LAUNCH_CHECK();
-  if (wsk) {
-    hipLaunchKernelGGL((partials_reduce3_kernel<T>), dim3(ceil_div(cols, 32), 2), dim3(256), 0, s, ws, ws + cols,
-                       (const float*)nullptr, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (T*)dw,
-                       (T*)db, (T*)nullptr, grid, (int64_t)2 * cols, cols, accumulate);
+  const bool nt = ln_streams(rows, cols, sizeof(T));
+  return ln_with_route(cols, [&](auto ch, auto nw) {
+    constexpr int CH = decltype(ch)::value, NW = decltype(nw)::value;
+    const int grid = ln_grid(rows, NW, g_ln_blocks_bwd);
+    const size_t sh = (NW == 1) ? (size_t)4 * cols * sizeof(float) : 64;
+    const int rc = op_with_bool(nt, [&](auto ntc) {
+      hipLaunchKernelGGL((ln_bwd_kernel<T, CH, NW, GELU, decltype(ntc)::value>), dim3(grid), dim3(256), sh, s, (const T*)dy, (const T*)x,
+                         (const T*)w, (const T*)b, mean, rstd, (const T*)add, (T*)dx, wsk, rows, cols, xmap);
+      OP_LAUNCH_CHECK();
+      return OP_OK;
+    });
+    return rc != OP_OK || !wsk ? rc : ln_reduce_dw_db<T>(ws, dw, db, grid, cols, accumulate, s);
+  });
+}
+
+template <bool Q8>
+int ln_geglu_fwd_dispatch(const void* h0, const void* h1, int64_t ldh, const void* w, const void* b, void* y, float* mean, float* rstd,
+                          void* q8, float* q8_scale, int64_t rows, int cols, float eps, hipStream_t s) {
+  return ln_with_route(cols, [&](auto ch, auto nw) {
+    constexpr int CH = decltype(ch)::value, NW = decltype(nw)::value;
+    hipLaunchKernelGGL((ln_geglu_fwd_kernel<CH, NW, Q8>), dim3(ln_grid(rows, NW, OP_LN_GEGLU_BLOCKS_FWD)), dim3(NW == 1 ? 256 : 64 * NW), 0,
+                       s, (const bf16_t*)h0, (const bf16_t*)h1, ldh, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, mean, rstd, rows,
+                       cols, eps, (uint8_t*)q8, q8_scale);
     OP_LAUNCH_CHECK();
-  }
-  return OP_OK;
+    return OP_OK;
+  });
 }
 
 }  // namespace
@@ -676,15 +707,13 @@ int op_layernorm_fwd(const void* x, const void* w, const void* b, void* y, float
   OP_CHECK_ARG(rows >= 0 && cols > 0 && cols % 8 == 0, "layernorm_fwd: cols=%lld must be a positive multiple of 8",
                (long long)cols);
   if (rows == 0) return OP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == OP_DT_BF16)
-    return act_gelu ? ln_fwd_dispatch<bf16_t, true>(x, w, b, y, mean, rstd, rows, (int)cols, eps, s, x_rows)
-                    : ln_fwd_dispatch<bf16_t, false>(x, w, b, y, mean, rstd, rows, (int)cols, eps, s, x_rows);
-  if (dtype == OP_DT_F32)
-    return act_gelu ? ln_fwd_dispatch<float, true>(x, w, b, y, mean, rstd, rows, (int)cols, eps, s, x_rows)
-                    : ln_fwd_dispatch<float, false>(x, w, b, y, mean, rstd, rows, (int)cols, eps, s, x_rows);
-  op_set_error("layernorm_fwd: bad dtype %d", dtype);
-  return OP_EINVAL;
+  OP_CHECK_ARG(dtype == OP_DT_BF16 || dtype == OP_DT_F32, "layernorm_fwd: bad dtype %d", dtype);
+  return op_with_bool(dtype == OP_DT_BF16, [&](auto bf) {
+    return op_with_bool(act_gelu != 0, [&](auto gelu) {
+      return ln_fwd_dispatch<op_elem_t<decltype(bf)::value>, decltype(gelu)::value>(x, w, b, y, mean, rstd, rows, (int)cols, eps,
+                                                                                   (hipStream_t)stream, x_rows);
+    });
+  });
 }
 
 // op_layernorm_fwd for bf16 without GELU that ALSO writes the output row-quantised to fp8 e4m3: q8 [rows, cols] bytes and
@@ -695,20 +724,7 @@ int op_layernorm_fwd_q8(const void* x, const void* w, const void* b, void* y, fl
   OP_CHECK_ARG(x && y && q8 && q8_scale, "layernorm_fwd_q8: null pointer");
   OP_CHECK_ARG(rows >= 0 && cols > 0 && cols % 8 == 0 && cols <= 8192, "layernorm_fwd_q8: cols=%lld unsupported", (long long)cols);
   if (rows == 0) return OP_OK;
-  hipStream_t s = (hipStream_t)stream;
-#define LN_Q(CH, NW)                                                                                                                         \
-  hipLaunchKernelGGL((ln_fwd_kernel<bf16_t, CH, NW, false, false, true>), dim3(ln_grid(rows, NW, g_ln_blocks_fwd)), dim3(256), 0, s,        \
-                     (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, mean, rstd, rows, (int)cols, eps, (uint8_t*)q8, q8_scale)
-  if (cols <= 512) LN_Q(1, 1);
-  else if (cols <= 1024) LN_Q(2, 1);
-  else if (cols <= 1536) LN_Q(3, 1);
-  else if (cols <= 2048) LN_Q(4, 1);
-  else if (cols <= 4096) LN_Q(2, 4);
-  else if (cols <= 6144) LN_Q(3, 4);
-  else LN_Q(4, 4);
-#undef LN_Q
-  OP_LAUNCH_CHECK();
-  return OP_OK;
+  return ln_fwd_dispatch<bf16_t, false, true>(x, w, b, y, mean, rstd, rows, (int)cols, eps, (hipStream_t)stream, nullptr, q8, q8_scale);
 }
 
 // dx = LN backward (+ add, the gradient arriving through the residual path, optional and may alias dx)
@@ -720,24 +736,15 @@ int op_layernorm_bwd(const void* dy, const void* x, const void* w, const void* b
                (long long)cols);
   OP_CHECK_ARG(!(dw || db) || workspace, "layernorm_bwd: dw/db requested without workspace");
   if (rows == 0) return OP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == OP_DT_BF16)
-    return act_gelu ? ln_bwd_dispatch<bf16_t, true>(dy, x, w, b, mean, rstd, add, dx, dw, db, (float*)workspace, rows,
-                                                    (int)cols, accumulate, s, x_rows)
-                    : ln_bwd_dispatch<bf16_t, false>(dy, x, w, b, mean, rstd, add, dx, dw, db, (float*)workspace, rows,
-                                                     (int)cols, accumulate, s, x_rows);
-  if (dtype == OP_DT_F32)
-    return act_gelu ? ln_bwd_dispatch<float, true>(dy, x, w, b, mean, rstd, add, dx, dw, db, (float*)workspace, rows,
-                                                   (int)cols, accumulate, s, x_rows)
-                    : ln_bwd_dispatch<float, false>(dy, x, w, b, mean, rstd, add, dx, dw, db, (float*)workspace, rows,
-                                                    (int)cols, accumulate, s, x_rows);
-  op_set_error("layernorm_bwd: bad dtype %d", dtype);
-  return OP_EINVAL;
+  OP_CHECK_ARG(dtype == OP_DT_BF16 || dtype == OP_DT_F32, "layernorm_bwd: bad dtype %d", dtype);
+  return op_with_bool(dtype == OP_DT_BF16, [&](auto bf) {
+    return op_with_bool(act_gelu != 0, [&](auto gelu) {
+      return ln_bwd_dispatch<op_elem_t<decltype(bf)::value>, decltype(gelu)::value>(
+          dy, x, w, b, mean, rstd, add, dx, dw, db, (float*)workspace, rows, (int)cols, accumulate, (hipStream_t)stream, x_rows);
+    });
+  });
 }
 
-// Backward of  y = LayerNorm_F(gelu(h0) * h1) * w + b  w.r.t. h0, h1, w, b in one pass (bf16 only); mean/rstd are the
-// forward statistics of g = gelu(h0) * h1.  Replaces the LayerNorm backward + GeGLU backward pair of the FFN
-// (one_peace/models/transformer/transformer_layer.py:64-67,111-118); g itself is not needed.
 // y [rows, cols] = LayerNorm(bf16(gelu(h0) * h1)) (+ mean / rstd, nullable); h0, h1: row stride ldh (0 = cols).
 int op_ln_geglu_fwd(const void* h0, const void* h1, int64_t ldh, const void* w, const void* b, void* y, float* mean, float* rstd,
                     int64_t rows, int64_t cols, float eps, void* stream) {
@@ -746,21 +753,7 @@ int op_ln_geglu_fwd(const void* h0, const void* h1, int64_t ldh, const void* w, 
   OP_CHECK_ARG(rows >= 0 && cols > 0 && cols % 8 == 0 && cols <= 8192 && ldh >= cols && ldh % 8 == 0, "ln_geglu_fwd: cols=%lld ldh=%lld unsupported",
                (long long)cols, (long long)ldh);
   if (rows == 0) return OP_OK;
-  hipStream_t s = (hipStream_t)stream;
-#define LNG_F(CH, NW)                                                                                                       \
-  hipLaunchKernelGGL((ln_geglu_fwd_kernel<CH, NW>), dim3(ln_grid(rows, NW, OP_LN_GEGLU_BLOCKS_FWD)), dim3(NW == 1 ? 256 : 64 * NW), 0, s, \
-                     (const bf16_t*)h0, (const bf16_t*)h1, ldh, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, mean, rstd, rows, \
-                     (int)cols, eps)
-  if (cols <= 512) LNG_F(1, 1);
-  else if (cols <= 1024) LNG_F(2, 1);
-  else if (cols <= 1536) LNG_F(3, 1);
-  else if (cols <= 2048) LNG_F(4, 1);
-  else if (cols <= 4096) LNG_F(2, 4);
-  else if (cols <= 6144) LNG_F(3, 4);
-  else LNG_F(4, 4);
-#undef LNG_F
-  OP_LAUNCH_CHECK();
-  return OP_OK;
+  return ln_geglu_fwd_dispatch<false>(h0, h1, ldh, w, b, y, mean, rstd, nullptr, nullptr, rows, (int)cols, eps, (hipStream_t)stream);
 }
 
 // op_ln_geglu_fwd that also writes the row-quantised fp8 copy of its output (see op_layernorm_fwd_q8): the operand of the fp8 down-projection.
@@ -771,23 +764,12 @@ int op_ln_geglu_fwd_q8(const void* h0, const void* h1, int64_t ldh, const void* 
   OP_CHECK_ARG(rows >= 0 && cols > 0 && cols % 8 == 0 && cols <= 8192 && ldh >= cols && ldh % 8 == 0, "ln_geglu_fwd_q8: cols=%lld ldh=%lld unsupported",
                (long long)cols, (long long)ldh);
   if (rows == 0) return OP_OK;
-  hipStream_t s = (hipStream_t)stream;
-#define LNG_Q(CH, NW)                                                                                                       \
-  hipLaunchKernelGGL((ln_geglu_fwd_kernel<CH, NW, true>), dim3(ln_grid(rows, NW, OP_LN_GEGLU_BLOCKS_FWD)), dim3(NW == 1 ? 256 : 64 * NW), 0, s, \
-                     (const bf16_t*)h0, (const bf16_t*)h1, ldh, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, mean, rstd, rows, \
-                     (int)cols, eps, (uint8_t*)q8, q8_scale)
-  if (cols <= 512) LNG_Q(1, 1);
-  else if (cols <= 1024) LNG_Q(2, 1);
-  else if (cols <= 1536) LNG_Q(3, 1);
-  else if (cols <= 2048) LNG_Q(4, 1);
-  else if (cols <= 4096) LNG_Q(2, 4);
-  else if (cols <= 6144) LNG_Q(3, 4);
-  else LNG_Q(4, 4);
-#undef LNG_Q
-  OP_LAUNCH_CHECK();
-  return OP_OK;
+  return ln_geglu_fwd_dispatch<true>(h0, h1, ldh, w, b, y, mean, rstd, q8, q8_scale, rows, (int)cols, eps, (hipStream_t)stream);
 }
 
+// Backward of  y = LayerNorm_F(gelu(h0) * h1) * w + b  w.r.t. h0, h1, w, b in one pass (bf16 only); mean/rstd are the
+// forward statistics of g = gelu(h0) * h1.  Replaces the LayerNorm backward + GeGLU backward pair of the FFN
+// (one_peace/models/transformer/transformer_layer.py:64-67,111-118); g itself is not needed.
 int op_ln_geglu_bwd(const void* dy, const void* h0, const void* h1, const void* w, const float* mean, const float* rstd,
                     void* dh0, void* dh1, int64_t ldd, int64_t ldh, void* dw, void* db, void* workspace, int64_t rows, int64_t cols,
                     int accumulate, void* stream) {
@@ -800,31 +782,16 @@ int op_ln_geglu_bwd(const void* dy, const void* h0, const void* h1, const void* 
   if (rows == 0) return OP_OK;
   hipStream_t s = (hipStream_t)stream;
   float* wsk = (dw || db) ? (float*)workspace : nullptr;
-  int grid = 0;
-#define LNG_B(CH, NW)                                                                                              \
-  do {                                                                                                             \
-    grid = ln_grid(rows, NW, OP_LN_GEGLU_BLOCKS_BWD);                                                                     \
-    size_t sh = (NW == 1) ? (size_t)4 * cols * sizeof(float) : 64;                                                 \
-    hipLaunchKernelGGL((ln_geglu_bwd_kernel<CH, NW>), dim3(grid), dim3(NW == 1 ? 256 : 64 * NW), sh, s,           \
-                       (const bf16_t*)dy, (const bf16_t*)h0, (const bf16_t*)h1, (const bf16_t*)w, mean, rstd,      \
-                       (bf16_t*)dh0, (bf16_t*)dh1, ldd, ldh, wsk, rows, (int)cols);                                \
-  } while (0)
-  if (cols <= 512) LNG_B(1, 1);
-  else if (cols <= 1024) LNG_B(2, 1);
-  else if (cols <= 1536) LNG_B(3, 1);
-  else if (cols <= 2048) LNG_B(4, 1);
-  else if (cols <= 4096) LNG_B(2, 4);
-  else if (cols <= 6144) LNG_B(3, 4);
-  else LNG_B(4, 4);
-#undef LNG_B
-  OP_LAUNCH_CHECK();
-  if (wsk) {
-    hipLaunchKernelGGL((partials_reduce3_kernel<bf16_t>), dim3(ceil_div(cols, 32), 2), dim3(256), 0, s, wsk, wsk + cols,
-                       (const float*)nullptr, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (const bf16_t*)nullptr,
-                       (bf16_t*)dw, (bf16_t*)db, (bf16_t*)nullptr, grid, (int64_t)2 * cols, (int)cols, accumulate);
+  return ln_with_route((int)cols, [&](auto ch, auto nw) {
+    constexpr int CH = decltype(ch)::value, NW = decltype(nw)::value;
+    const int grid = ln_grid(rows, NW, OP_LN_GEGLU_BLOCKS_BWD);
+    const size_t sh = (NW == 1) ? (size_t)4 * cols * sizeof(float) : 64;
+    hipLaunchKernelGGL((ln_geglu_bwd_kernel<CH, NW>), dim3(grid), dim3(NW == 1 ? 256 : 64 * NW), sh, s, (const bf16_t*)dy,
+                       (const bf16_t*)h0, (const bf16_t*)h1, (const bf16_t*)w, mean, rstd, (bf16_t*)dh0, (bf16_t*)dh1, ldd, ldh, wsk,
+                       rows, (int)cols);
     OP_LAUNCH_CHECK();
-  }
-  return OP_OK;
+    return wsk ? ln_reduce_dw_db<bf16_t>(wsk, dw, db, grid, (int)cols, accumulate, s) : OP_OK;
+  });
 }
 
 }  // extern "C"

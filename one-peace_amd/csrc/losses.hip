@@ -386,19 +386,16 @@ extern "C" int op_row_loss(const void* logits, int dtype, int64_t ld, const void
   if (B == 0) return OP_OK;
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)B), block(RL_THREADS);
-#define RL_LAUNCH(T, TT)                                                                                                            \
-  hipLaunchKernelGGL((row_loss_kernel<T, TT>), grid, block, 0, st, (const T*)logits, ld, targets, ld_targets, (int)C, mode,          \
-                     label_smoothing, margin, gscale, row_loss, row_correct, dlogits)
-  const bool tb = dense && target_dtype == OP_DT_BF16;
-  if (dtype == OP_DT_BF16) {
-    if (tb) RL_LAUNCH(bf16_t, bf16_t);
-    else RL_LAUNCH(bf16_t, float);
-  } else {
-    if (tb) RL_LAUNCH(float, bf16_t);
-    else RL_LAUNCH(float, float);
-  }
-#undef RL_LAUNCH
-  OP_LAUNCH_CHECK();
+  const int rc = op_with_bool(dtype == OP_DT_BF16, [&](auto xb) {
+    return op_with_bool(dense && target_dtype == OP_DT_BF16, [&](auto tb) {
+      typedef op_elem_t<decltype(xb)::value> T;
+      hipLaunchKernelGGL((row_loss_kernel<T, op_elem_t<decltype(tb)::value>>), grid, block, 0, st, (const T*)logits, ld, targets, ld_targets,
+                         (int)C, mode, label_smoothing, margin, gscale, row_loss, row_correct, dlogits);
+      OP_LAUNCH_CHECK();
+      return OP_OK;
+    });
+  });
+  if (rc != OP_OK) return rc;
   if (sums) {
     hipLaunchKernelGGL(sum_rows_kernel, dim3(1), block, 0, st, (const float*)row_loss, (const float*)row_correct, B, sums);
     OP_LAUNCH_CHECK();

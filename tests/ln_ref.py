@@ -70,9 +70,10 @@ MIB64 = 64 << 20
 # ----------------------------------------------------------------------------------------------------------------------
 # the mirror of the dispatch
 # ----------------------------------------------------------------------------------------------------------------------
-# MIRROR of csrc/layernorm.hip: ln_fwd_dispatch / ln_bwd_dispatch (the cols ladder and the non-temporal rule), op_layernorm_fwd_q8,
-# op_ln_geglu_fwd(_q8), op_ln_geglu_bwd (the same ladder), ln_grid, and the caps g_ln_blocks_fwd, g_ln_blocks_bwd (512),
-# OP_LN_GEGLU_BLOCKS_FWD (2048), OP_LN_GEGLU_BLOCKS_BWD (512).  A build that overrides the macros changes which route a case reaches,
+# MIRROR of csrc/layernorm.hip: LN_ROUTES / ln_route / ln_with_route (the cols ladder every entry point goes through), ln_streams with
+# ln_fwd_dispatch / ln_bwd_dispatch (the non-temporal rule; never for the q8 forward, always for ln_geglu_fwd_dispatch and
+# op_ln_geglu_bwd), ln_grid, and the caps g_ln_blocks_fwd, g_ln_blocks_bwd (512), OP_LN_GEGLU_BLOCKS_FWD (2048),
+# OP_LN_GEGLU_BLOCKS_BWD (512).  A build that overrides the macros changes which route a case reaches,
 # not whether the case is correct.
 CAPS = {"fwd": 512, "fwd_q8": 512, "bwd": 512, "geglu_fwd": 2048, "geglu_fwd_q8": 2048, "geglu_bwd": 512}
 
@@ -560,10 +561,15 @@ def _cases():
     add("C", "ln", 2049, 4104, family="normal")
     for cols in (520, 1536, 2048) + B_COLS:     # one trip on the classes the three widths above do not reach
         add("C", "ln", 5, cols, family="outlier")
+    for cols in (512, 1024, 4096):     # the widest row of the three classes whose maximum no case above reaches
+        add("C", "ln", 5, cols, family="outlier")
     # D: the GeGLU pair
     for i, cols in enumerate(A_COLS):
         add("D", "geglu_fwd", 8197, cols, family=fams[i % 7])
         add("D", "geglu_bwd", A_ROWS, cols, family=fams[(i + 4) % 7], dyfam=("normal", "rowscale")[i % 2])
+        add("D", "geglu_fwd", 5, cols, family="gelu_tails")
+        add("D", "geglu_bwd", 5, cols, family="gelu_tails")
+    for cols in (512, 1024, 4096):     # (as in group C: the class maxima no other width reaches)
         add("D", "geglu_fwd", 5, cols, family="gelu_tails")
         add("D", "geglu_bwd", 5, cols, family="gelu_tails")
     for i, cols in enumerate((2056, 6144)):

@@ -322,8 +322,11 @@ def test_ln_geglu_bwd(case):
     run.finish()
 
 
-# ---- the fp8 copies at three trips --------------------------------------------------------------------------------------
-@pytest.mark.parametrize("rows,cols", [(L.A_ROWS, 520), (L.B_ROWS, 4104)])
+# ---- the fp8 copies at three trips, and one trip at the widest row of every (CH, NW) class ---------------------------------
+Q8_WIDEST = [(5, cols) for cols in (512, 1024, 1536, 2048, 4096, 6144, 8192)]
+
+
+@pytest.mark.parametrize("rows,cols", [(L.A_ROWS, 520), (L.B_ROWS, 4104)] + Q8_WIDEST)
 def test_layernorm_q8(rows, cols):
     hip = hipmod()
     run = Run("q8-ln-%dx%d" % (rows, cols), "fwd_q8=%s" % (L.route("fwd_q8", rows, cols),))
@@ -347,7 +350,7 @@ def test_layernorm_q8(rows, cols):
     run.finish()
 
 
-@pytest.mark.parametrize("rows,cols", [(8197, 520), (2053, 2056), (16389, 72), (4101, 2056), (16389, 2048)])
+@pytest.mark.parametrize("rows,cols", [(8197, 520), (2053, 2056), (16389, 72), (4101, 2056), (16389, 2048)] + Q8_WIDEST)
 def test_ln_geglu_q8(rows, cols):
     hip = hipmod()
     run = Run("q8-geglu-%dx%d" % (rows, cols), "geglu_fwd_q8=%s" % (L.route("geglu_fwd_q8", rows, cols),))
