@@ -395,6 +395,23 @@ int op_adamw_step_groups_ema(void* p, float* master, const void* g, float* m, fl
                              const int64_t* group_end8, const float* group_lr_scale, const float* group_weight_decay,
                              int64_t n_groups, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
                              const float* grad_sqnorm, float clip_norm, float ema_keep, float ema_take, void* stream);
+/* The grouped step over ONE RANGE of the flat buffers: the optimiser state sharded over the data-parallel ranks, what the reference
+ * runs with `use_distributed_fused_adam: true` (one_peace/optim/adam.py:58-70 -> optim/distributed_fused_adam.py: apex's
+ * DistributedFusedAdam partitions the state, every rank updates its partition, the parameters are gathered afterwards).
+ * p, g: bases of the FULL flat bf16 buffers of numel elements (numel % 8 == 0).  The vectors [first8, first8 + count8) are updated,
+ * nothing else of p is touched and g is only read.  m, v, master, ema: fp32 buffers of the RANGE, 8 * count8 elements each, local
+ * vector 0 = global vector first8; master and ema may each be NULL (the four arrangements of op_adamw_step_groups, _master and
+ * _ema; ema_keep / ema_take are unused without ema).  group_end8 / group_lr_scale / group_weight_decay: the GLOBAL tables of
+ * op_adamw_step_groups, unshifted.  grad_sqnorm: the sum of squares of the FULL gradient buffer.  Every element of the range
+ * receives bit for bit what the whole-buffer entry of the same arrangement stores for it: the same kernel runs, with the range's
+ * global start added to the vector index for the group lookup only.
+ * Refused, with nothing launched: a null p, g, m, v or table; numel % 8 != 0; first8 < 0; count8 < 0; first8 + count8 > numel / 8;
+ * n_groups outside 1..256; step < 1; ema overlapping master.  count8 == 0 returns OP_OK without a launch.
+ * Additive: op_abi_version() stays 10. */
+int op_adamw_step_shard(void* p, const void* g, int64_t numel, int64_t first8, int64_t count8, float* m, float* v, float* master,
+                        float* ema, const int64_t* group_end8, const float* group_lr_scale, const float* group_weight_decay,
+                        int64_t n_groups, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
+                        const float* grad_sqnorm, float clip_norm, float ema_keep, float ema_take, void* stream);
 /* out[0] = sum of squares of a bf16 vector in fp32 (the global gradient norm of fairseq/fairseq/utils.py:349-391 over the
  * flat gradient buffer; feeds op_adamw_step's device-side clip coefficient, trainer.py:929).  workspace: 1024 floats. */
 int op_sqnorm(const void* x, int64_t numel, float* workspace, float* out, void* stream);

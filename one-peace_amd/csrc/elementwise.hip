@@ -476,6 +476,10 @@ __global__ __launch_bounds__(256) void ema_step_kernel(float* __restrict__ e, co
 //           instead of being rounded away every step.
 //   EMA     the EMA pass folded in: one more fp32 stream e, and after the update ema_rule with the value the bf16 store of p
 //           rounds to -- also with a master: the reference's EMA reads the model, never the optimiser's fp32 copy.
+// first8 (runtime): the kernel may run over a RANGE of the flat buffer (op_adamw_step_shard: the optimiser state sharded over the
+// data-parallel ranks).  Every pointer then arrives at the range's first vector and is indexed from 0; first8, the global index of
+// that vector, is added to the loop index for the group lookup alone, so the table stays the global one and an element's update
+// does not depend on where the range starts.  The whole-buffer entries pass 0.
 // Algorithmic bytes per parameter: 22 plain or with GROUPS alone (p r+w 4, g r 2, m and v r+w 16); 28 with MASTER (master r+w 8,
 // g r 2, m and v r+w 16, p w 2); with EMA 30 without the master (22 + e r+w 8) and 36 with it (28 + 8).
 // Non-finite gradients with clipping on: a NaN anywhere in the gradient buffer makes the norm NaN, the clip coefficient NaN
@@ -503,7 +507,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(bf16_t* __restrict__ p, floa
                                                     const float* __restrict__ lr_scale, const float* __restrict__ wd,
                                                     int n_groups, float lr, float bias_corr, float step_size, float decay_mul,
                                                     float beta1, float beta2, float eps, float grad_scale,
-                                                    const float* __restrict__ sqnorm, float clip_norm, float keep, float take) {
+                                                    const float* __restrict__ sqnorm, float clip_norm, float keep, float take,
+                                                    int64_t first8) {
   __shared__ int64_t s_end[ADAM_MAX_GROUPS];  // unused, and not allocated, without GROUPS
   __shared__ float s_step[ADAM_MAX_GROUPS], s_decay[ADAM_MAX_GROUPS];
   if constexpr (GROUPS) {
@@ -520,11 +525,12 @@ __global__ __launch_bounds__(256) void adamw_kernel(bf16_t* __restrict__ p, floa
   int64_t lo = 0, hi = GROUPS ? s_end[0] : 0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
     if constexpr (GROUPS) {
-      if (i < lo || i >= hi) {  // first group whose end is > i
+      const int64_t gi = i + first8;  // the vector's place in the whole flat buffer: what the table speaks of
+      if (gi < lo || gi >= hi) {  // first group whose end is > gi
         int a = 0, b = n_groups - 1;
         while (a < b) {
           const int mid = (a + b) >> 1;
-          if (s_end[mid] > i) b = mid; else a = mid + 1;
+          if (s_end[mid] > gi) b = mid; else a = mid + 1;
         }
         grp = a;
         lo = grp ? s_end[grp - 1] : 0;
@@ -1024,13 +1030,15 @@ int op_sqnorm(const void* x, int64_t numel, float* workspace, float* out, void* 
   return OP_OK;
 }
 
-// What the four op_adamw_step* entries share: the argument checks (messages carry the entry's prefix `who`), the bias correction
+// What the five op_adamw_step* entries share: the argument checks (messages carry the entry's prefix `who`), the bias correction
 // and the launch of adamw_kernel<groups, master != NULL, ema != NULL>.  An entry that requires master or ema checks that itself.
 // Without groups step_size and decay_mul are formed here, step_size in fp64 and rounded once; with groups the device forms them.
+// numel is the length of what the pointers address and first8 the global index of its first vector (0 but for op_adamw_step_shard).
 static int adamw_launch(const char* who, bool groups, void* p, float* master, const void* g, float* m, float* v, float* ema,
-                        int64_t numel, const int64_t* group_end8, const float* group_lr_scale, const float* group_weight_decay,
-                        int64_t n_groups, float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
-                        float grad_scale, const float* grad_sqnorm, float clip_norm, float ema_keep, float ema_take, void* stream) {
+                        int64_t numel, int64_t first8, const int64_t* group_end8, const float* group_lr_scale,
+                        const float* group_weight_decay, int64_t n_groups, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int64_t step, float grad_scale, const float* grad_sqnorm, float clip_norm, float ema_keep,
+                        float ema_take, void* stream) {
   OP_CHECK_ARG(p && g && m && v && (!groups || (group_end8 && group_lr_scale && group_weight_decay)), "%s: null pointer", who);
   OP_CHECK_ARG(numel % 8 == 0 && step >= 1 && (!groups || (n_groups >= 1 && n_groups <= ADAM_MAX_GROUPS)),
                groups ? "%s: numel %% 8 == 0, step >= 1, 1 <= n_groups <= %d required" : "%s: numel must be a multiple of 8 and step >= 1",
@@ -1047,7 +1055,7 @@ static int adamw_launch(const char* who, bool groups, void* p, float* master, co
   hipLaunchKernelGGL((groups ? with_groups[(master != nullptr) + 2 * (ema != nullptr)] : adamw_kernel<false, false, false>),
                      dim3(ew_grid(numel / 8)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)p, master, (const bf16_t*)g, m, v, ema,
                      numel / 8, group_end8, group_lr_scale, group_weight_decay, (int)n_groups, lr, bias_corr, step_size, decay_mul,
-                     beta1, beta2, eps, grad_scale, grad_sqnorm, clip_norm, ema_keep, ema_take);
+                     beta1, beta2, eps, grad_scale, grad_sqnorm, clip_norm, ema_keep, ema_take, first8);
   OP_LAUNCH_CHECK();
   return OP_OK;
 }
@@ -1059,7 +1067,7 @@ static int adamw_launch(const char* who, bool groups, void* p, float* master, co
 int op_adamw_step(void* p, const void* g, float* m, float* v, int64_t numel, float lr, float beta1, float beta2, float eps,
                   float weight_decay, int64_t step, float grad_scale, const float* grad_sqnorm, float clip_norm,
                   void* stream) {
-  return adamw_launch("adamw", false, p, nullptr, g, m, v, nullptr, numel, nullptr, nullptr, nullptr, 0, lr, beta1, beta2, eps,
+  return adamw_launch("adamw", false, p, nullptr, g, m, v, nullptr, numel, 0, nullptr, nullptr, nullptr, 0, lr, beta1, beta2, eps,
                       weight_decay, step, grad_scale, grad_sqnorm, clip_norm, 0.f, 0.f, stream);
 }
 
@@ -1071,7 +1079,7 @@ int op_adamw_step_groups(void* p, const void* g, float* m, float* v, int64_t num
                          const float* group_lr_scale, const float* group_weight_decay, int64_t n_groups, float lr, float beta1,
                          float beta2, float eps, int64_t step, float grad_scale, const float* grad_sqnorm, float clip_norm,
                          void* stream) {
-  return adamw_launch("adamw_groups", true, p, nullptr, g, m, v, nullptr, numel, group_end8, group_lr_scale, group_weight_decay,
+  return adamw_launch("adamw_groups", true, p, nullptr, g, m, v, nullptr, numel, 0, group_end8, group_lr_scale, group_weight_decay,
                       n_groups, lr, beta1, beta2, eps, 0.f, step, grad_scale, grad_sqnorm, clip_norm, 0.f, 0.f, stream);
 }
 
@@ -1082,7 +1090,7 @@ int op_adamw_step_groups_master(void* p, float* master, const void* g, float* m,
                                 int64_t n_groups, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
                                 const float* grad_sqnorm, float clip_norm, void* stream) {
   OP_CHECK_ARG(master, "adamw_groups_master: null pointer");
-  return adamw_launch("adamw_groups_master", true, p, master, g, m, v, nullptr, numel, group_end8, group_lr_scale,
+  return adamw_launch("adamw_groups_master", true, p, master, g, m, v, nullptr, numel, 0, group_end8, group_lr_scale,
                       group_weight_decay, n_groups, lr, beta1, beta2, eps, 0.f, step, grad_scale, grad_sqnorm, clip_norm, 0.f, 0.f,
                       stream);
 }
@@ -1105,8 +1113,24 @@ int op_adamw_step_groups_ema(void* p, float* master, const void* g, float* m, fl
                              int64_t n_groups, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
                              const float* grad_sqnorm, float clip_norm, float ema_keep, float ema_take, void* stream) {
   OP_CHECK_ARG(ema, "adamw_groups_ema: null pointer");
-  return adamw_launch("adamw_groups_ema", true, p, master, g, m, v, ema, numel, group_end8, group_lr_scale, group_weight_decay,
+  return adamw_launch("adamw_groups_ema", true, p, master, g, m, v, ema, numel, 0, group_end8, group_lr_scale, group_weight_decay,
                       n_groups, lr, beta1, beta2, eps, 0.f, step, grad_scale, grad_sqnorm, clip_norm, ema_keep, ema_take, stream);
+}
+
+// The grouped step over ONE RANGE of the flat buffers (include/onepeace_hip.h): p and g are the bases of the full buffers, m, v,
+// master and ema belong to the range alone.  The same kernel and the same global tables as the whole-buffer entries; only the
+// pointers are moved to the range here, and the kernel learns where it starts.  The range checks come before any pointer is moved.
+int op_adamw_step_shard(void* p, const void* g, int64_t numel, int64_t first8, int64_t count8, float* m, float* v, float* master,
+                        float* ema, const int64_t* group_end8, const float* group_lr_scale, const float* group_weight_decay,
+                        int64_t n_groups, float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale,
+                        const float* grad_sqnorm, float clip_norm, float ema_keep, float ema_take, void* stream) {
+  OP_CHECK_ARG(p && g, "adamw_shard: null pointer");
+  OP_CHECK_ARG(numel >= 0 && numel % 8 == 0, "adamw_shard: numel must be a multiple of 8");
+  OP_CHECK_ARG(first8 >= 0 && count8 >= 0 && first8 <= numel / 8 && count8 <= numel / 8 - first8,
+               "adamw_shard: the range [first8, first8 + count8) must lie inside [0, numel / 8)");
+  return adamw_launch("adamw_shard", true, (bf16_t*)p + first8 * 8, master, (const bf16_t*)g + first8 * 8, m, v, ema, count8 * 8,
+                      first8, group_end8, group_lr_scale, group_weight_decay, n_groups, lr, beta1, beta2, eps, 0.f, step, grad_scale,
+                      grad_sqnorm, clip_norm, ema_keep, ema_take, stream);
 }
 
 // transposed != 0 writes out[h][key][query] (the image the dK/dV kernel reads) instead of out[h][query][key]

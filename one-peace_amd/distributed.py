@@ -139,6 +139,107 @@ class FlatParameters:
             p._op_pending = 0
 
 
+class ShardLayout(collections.namedtuple("ShardLayout", "numel world rank shard8 tail8")):
+    """Which part of a flat buffer of ``numel`` elements rank ``rank`` of ``world`` keeps optimiser state for (``shard_layout``).
+    Counts ending in 8 are in 8-element vectors.  A buffer of the rank, ``[shard | tail]``, has ``local_numel`` elements."""
+    __slots__ = ()
+
+    @property
+    def first8(self):
+        return self.rank * self.shard8
+
+    @property
+    def tail_first8(self):
+        return self.world * self.shard8
+
+    @property
+    def local_numel(self):
+        return 8 * (self.shard8 + self.tail8)
+
+    @property
+    def gathered_numel(self):
+        """The elements an all-gather of the shards covers: [0, world * shard8 * 8)."""
+        return 8 * self.world * self.shard8
+
+    @property
+    def ranges(self):
+        """[(global start, global end, local start)] in elements: the own shard, then the replicated tail; empty ones left out."""
+        out = [(8 * self.first8, 8 * (self.first8 + self.shard8), 0), (8 * self.tail_first8, self.numel, 8 * self.shard8)]
+        return [r for r in out if r[1] > r[0]]
+
+    def take(self, full):
+        """The rank's ``[shard | tail]`` of a full-length tensor, as a new tensor."""
+        return torch.cat([full[a:b] for a, b, _ in self.ranges]) if self.ranges else full[:0].clone()
+
+
+def shard_layout(numel, world, rank):
+    """The partition of a flat buffer over data-parallel ranks for ``optim.ShardedFusedAdamW`` and the sharded ``ema.FlatEMA``
+    (the reference: optim/adam.py:58-70 -> apex's DistributedFusedAdam).  With numel8 = numel // 8 and shard8 = numel8 // world,
+    rank r owns the vectors [r * shard8, (r + 1) * shard8); the tail [world * shard8, numel8), fewer than ``world`` vectors, is
+    REPLICATED: every rank keeps state for it and updates it, all to the same bits.  So all shards have one length, one
+    ``all_gather_into_tensor`` serves, nothing is padded and ``FlatParameters`` does not know.  At world 1 the shard is everything."""
+    if numel < 0 or numel % FlatParameters.ALIGN:
+        raise ValueError("shard_layout: numel %d is not a multiple of %d" % (numel, FlatParameters.ALIGN))
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("shard_layout: rank %d of world %d" % (rank, world))
+    numel8 = numel // FlatParameters.ALIGN
+    shard8 = numel8 // world
+    return ShardLayout(numel, world, rank, shard8, numel8 - world * shard8)
+
+
+def resolve_shard(rank, world, process_group=None):
+    """(rank, world) of a sharded object: the process group's unless given.  Explicit values without an initialised group are
+    allowed (one process standing in for a rank: tests); with a group they must be the group's."""
+    live = dist.is_available() and dist.is_initialized()
+    if live:
+        gr, gw = dist.get_rank(process_group), dist.get_world_size(process_group)
+        if (rank is not None and rank != gr) or (world is not None and world != gw):
+            raise ValueError("rank %r of world %r given, the process group says rank %d of %d" % (rank, world, gr, gw))
+        return gr, gw
+    if (rank is None) != (world is None):
+        raise ValueError("give both rank and world, or neither")
+    return (0, 1) if rank is None else (int(rank), int(world))
+
+
+def _collective_group(layout, process_group, what):
+    """True when a collective has to run; False when there is nobody to talk to (world 1 without an initialised group)."""
+    if dist.is_available() and dist.is_initialized():
+        if dist.get_world_size(process_group) != layout.world or dist.get_rank(process_group) != layout.rank:
+            raise RuntimeError("%s: the layout is rank %d of %d, the process group is not" % (what, layout.rank, layout.world))
+        return True
+    if layout.world > 1:
+        raise RuntimeError("%s is collective: world %d needs an initialised process group" % (what, layout.world))
+    return False
+
+
+@torch.no_grad()
+def gather_shards(buf, layout, process_group=None):
+    """Every rank's shard of the full-length ``buf`` (each rank has written its own) into every rank's ``buf``: ONE
+    ``all_gather_into_tensor`` over ``buf[:world * shard8 * 8]``.  Over RCCL it runs in place (the send buffer is the rank's slot of
+    the receive buffer, which NCCL's all-gather defines); on another backend, where that aliasing is not promised, the own slice is
+    sent from a clone.  The tail is replicated and needs no communication."""
+    if not _collective_group(layout, process_group, "gather_shards") or layout.shard8 == 0:
+        return
+    k = 8 * layout.shard8
+    mine = buf[layout.rank * k:(layout.rank + 1) * k]
+    if not (buf.is_cuda and dist.get_backend(process_group) == "nccl"):
+        mine = mine.clone()
+    dist.all_gather_into_tensor(buf[:layout.gathered_numel], mine, group=process_group)
+
+
+@torch.no_grad()
+def gather_full(local, layout, process_group=None):
+    """The full-length tensor of which every rank holds ``[shard | tail]`` in ``local``.  Collective; the same on every rank."""
+    out = torch.empty(layout.numel, dtype=local.dtype, device=local.device)
+    k = 8 * layout.shard8
+    if _collective_group(layout, process_group, "gather_full") and k:
+        dist.all_gather_into_tensor(out[:layout.gathered_numel], local[:k].contiguous(), group=process_group)
+    else:
+        out[:k].copy_(local[:k])
+    out[layout.gathered_numel:].copy_(local[k:])
+    return out
+
+
 class BucketedGradReducer:
     """Asynchronous SUM all-reduce of contiguous gradient buckets, each launched when its last gradient is final.
 

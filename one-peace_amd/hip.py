@@ -72,6 +72,8 @@ SIGNATURES = {
     "op_ema_step": (c_int, [P, P, I64, c_float, c_float, P]),
     "op_adamw_step_groups_ema": (c_int, [P, P, P, P, P, P, I64, P, P, P, I64, c_float, c_float, c_float, c_float, I64, c_float, P,
                                         c_float, c_float, c_float, P]),
+    "op_adamw_step_shard": (c_int, [P, P, I64, I64, I64, P, P, P, P, P, P, P, I64, c_float, c_float, c_float, c_float, I64, c_float, P,
+                                   c_float, c_float, c_float, P]),
     "op_sqnorm": (c_int, [P, I64, P, P, P]),
     "op_relpos_bias_build": (c_int, [P, P, I64, P, I64, I64, I64, c_int, P]),
     "op_relpos_bias_bwd": (c_int, [P, I64, I64, P, P, I64, P, I64, P, P, I64, P]),
@@ -841,6 +843,27 @@ def adamw_step_groups_ema(p, master, g, m, v, ema, group_end8, group_lr_scale, g
                                           ptr(group_lr_scale), ptr(group_wd), group_end8.numel(), lr, beta1, beta2, eps, step,
                                           grad_scale, ptr(grad_sqnorm), clip_norm, ema_keep, ema_take, stream()),
            "op_adamw_step_groups_ema")
+
+
+def adamw_step_shard(p, g, first8, count8, m, v, master, ema, group_end8, group_lr_scale, group_wd, lr, beta1, beta2, eps, step,
+                     ema_keep=0.0, ema_take=0.0, grad_scale=1.0, grad_sqnorm=None, clip_norm=0.0):
+    """The grouped step over the vectors [first8, first8 + count8) of the FULL flat buffers p and g (optim.ShardedFusedAdamW): m, v and
+    the optional master and ema are fp32 buffers of that range alone (8 * count8 elements); the group tables are the global ones.
+    count8 == 0 is the C entry's OP_OK without a launch; its empty buffers (torch gives them a null address) are not handed over."""
+    _req(p, "p", torch.bfloat16)
+    _req(g, "g", torch.bfloat16)
+    if g.numel() != p.numel():
+        raise RuntimeError("g has %d elements, p has %d" % (g.numel(), p.numel()))
+    for t, name in ((m, "m"), (v, "v"), (master, "master"), (ema, "ema")):
+        if t is not None:  # the kernel runs over 8 * count8 elements of each: a shorter buffer would be read and written out of bounds
+            _req(t, name, torch.float32)
+            if t.numel() != 8 * count8:
+                raise RuntimeError("%s has %d elements, the range has %d" % (name, t.numel(), 8 * count8))
+    if count8 == 0 and 0 <= first8 <= p.numel() // 8:
+        return
+    _check(lib().op_adamw_step_shard(ptr(p), ptr(g), p.numel(), first8, count8, ptr(m), ptr(v), ptr(master), ptr(ema), ptr(group_end8),
+                                     ptr(group_lr_scale), ptr(group_wd), group_end8.numel(), lr, beta1, beta2, eps, step, grad_scale,
+                                     ptr(grad_sqnorm), clip_norm, ema_keep, ema_take, stream()), "op_adamw_step_shard")
 
 
 def sqnorm(x, out=None):
