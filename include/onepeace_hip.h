@@ -575,6 +575,35 @@ int op_row_loss(const void* logits, int dtype, int64_t ld, const void* targets, 
  * a launch. */
 int op_box_loss(const void* logits, int dtype, const float* targets, int64_t B, float gscale, float* out, float* dlogits, void* stream);
 
+/* ---- single-query attention pooling of the fine-tuning head (csrc/attnpool.hip) ---------------------------------------------------
+ * Additive: op_abi_version() stays 10, no existing entry point changed.
+ * op_attn_pool_fwd replaces one_peace/models/one_peace/one_peace_base.py:157 and :160-170 (MultiheadAttentionPooling.forward between
+ * the K / V projections and out_proj: the expanded query, bmm, masked_fill_, fp32 softmax, bmm, reshape); op_attn_pool_bwd replaces
+ * the autograd backward of those lines.  The projections of :158-159 and :171 stay GEMMs of their own.
+ * k, v: bf16, element (b, s, h, d) at b * batch_stride + s * ld + h * hd + d (strides in elements): a [:, 1:, :] slice, or the two
+ * halves of one [B, S, 2 H] buffer, need no copy.  q: bf16 [heads * hd], one learned query per head.  pad: uint8 [B, ld_pad], non-zero
+ * = masked key, or NULL.  out: bf16 [B, heads * hd], dense.  p: fp32 [B, heads, S], the probabilities, kept for the backward.
+ *   scores  s_s = q_h . k[b, s, h, :] in fp32, WITHOUT a 1 / sqrt(hd) factor (the reference has none, :157-160)
+ *   p       = softmax over the unmasked keys in fp32, the maximum subtracted (expf, one division per key)
+ *   out     = sum_s p_s v[b, s, h, :] in fp32, rounded to bf16 once (to nearest even)
+ * op_attn_pool_bwd, with p as stored and c = sum_s p_s dp_s per (b, h):  dp_s = dout_h . v_s,  ds_s = p_s (dp_s - c),
+ * dv_s = p_s dout_h,  dk_s = ds_s q_h,  dq_part[b, h, :] = sum_s ds_s k_s.  dout: bf16 [B, heads * hd], dense.  dk, dv: bf16 with their
+ * own strides ldg / batch_stride_g; EVERY element of [B, S, heads * hd] is written.  dq_part: fp32 [B, heads * hd], one partial per
+ * sample: the caller sums it over B (no atomics).
+ * Masked keys -- a DEVIATION from the reference: a masked key gets p = 0 exactly and is skipped, not multiplied by zero; its rows of k
+ * and v are never read and its rows of dk and dv are zeros (the backward takes p_s == 0 as the mark).  A non-finite value in a masked row
+ * of k or v therefore reaches no output, where the reference's bmm turns it into NaN.  A sample whose keys are ALL masked gives NaN in
+ * p, out and its gradients, as in the reference (softmax over a row of -inf).
+ * Every sum runs in a fixed order: two runs give the same bits, and the results of sample b do not depend on B.
+ * Limits (OP_EINVAL with a message otherwise, nothing launched): hd % 8 == 0 and 8 <= hd <= 128; 1 <= S <= 4096; ld, ldg >= heads * hd;
+ * ld, ldg and the batch strides multiples of 8; batch_stride_g >= (S - 1) * ldg + heads * hd when B > 1; every bf16 pointer and dq_part
+ * aligned to 16 bytes; ld_pad >= S; B * heads < 2^31.  B == 0 returns without a launch.  Nothing is allocated or synchronised. */
+int op_attn_pool_fwd(const void* k, const void* v, int64_t ld, int64_t batch_stride, const void* q, const uint8_t* pad, int64_t ld_pad,
+                     void* out, float* p, int64_t B, int64_t S, int64_t heads, int64_t hd, void* stream);
+int op_attn_pool_bwd(const void* dout, const void* k, const void* v, int64_t ld, int64_t batch_stride, const void* q, const float* p,
+                     void* dk, void* dv, int64_t ldg, int64_t batch_stride_g, float* dq_part, int64_t B, int64_t S, int64_t heads,
+                     int64_t hd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,8 @@ SIGNATURES = {
     "op_average_precision": (c_int, [P, I64, P, I64, I64, I64, P, P, P, I64, P]),
     "op_row_loss": (c_int, [P, c_int, I64, P, c_int, I64, I64, I64, c_int, c_float, c_float, c_float, P, P, P, P, P]),
     "op_box_loss": (c_int, [P, c_int, P, I64, c_float, P, P, P]),
+    "op_attn_pool_fwd": (c_int, [P, P, I64, I64, P, P, I64, P, P, I64, I64, I64, I64, P]),
+    "op_attn_pool_bwd": (c_int, [P, P, P, I64, I64, P, P, P, P, I64, I64, P, I64, I64, I64, I64, P]),
 }
 
 
@@ -1314,6 +1316,77 @@ def box_loss(logits, targets, gscale=1.0, write_grad=True):
     dlogits = torch.empty(B, 4, dtype=torch.float32, device=logits.device) if write_grad else None
     _check(lib().op_box_loss(ptr(logits), _dt(logits), ptr(targets), B, gscale, ptr(out), ptr(dlogits), stream()), "op_box_loss")
     return out, dlogits
+
+
+ATTN_POOL_MAX_S = 4096  # csrc/attnpool.hip: AP_MAX_S
+
+
+def attn_pool_supported(k, v, heads, hd):
+    """The limits of op_attn_pool_fwd / _bwd for k, v [B, S, heads * hd] (any batch / row strides the kernel takes)."""
+    if k.dim() != 3 or k.shape != v.shape or k.shape[2] != heads * hd or k.stride() != v.stride():
+        return False
+    B, S, _ = k.shape
+    return (hd % 8 == 0 and 8 <= hd <= 128 and 1 <= S <= ATTN_POOL_MAX_S and B >= 1 and k.stride(2) == 1
+            and k.stride(1) % 8 == 0 and k.stride(1) >= heads * hd and k.stride(0) % 8 == 0 and k.stride(0) >= 0
+            and k.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0)
+
+
+def _attn_pool_kv(k, v, heads, hd):
+    for t, name in ((k, "k"), (v, "v")):
+        if not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 3 or t.stride(2) != 1:
+            raise RuntimeError("attn_pool: %s must be a bf16 CUDA(HIP) tensor [B, S, heads * hd] with unit column stride" % name)
+    if k.shape != v.shape or k.stride() != v.stride() or k.shape[2] != heads * hd:
+        raise RuntimeError("attn_pool: k %s / v %s must share shape and strides, last dim heads * hd = %d" % (
+            tuple(k.shape), tuple(v.shape), heads * hd))
+    B, S, _ = k.shape
+    ld = k.stride(1) if S > 1 else max(k.stride(1), heads * hd)     # (torch gives a size-1 dimension any stride)
+    bs = k.stride(0) if B > 1 else 0
+    return B, S, ld, bs
+
+
+def attn_pool_fwd(k, v, q, pad=None, out=None, p=None):
+    """op_attn_pool_fwd: k, v bf16 [B, S, heads * hd] (shared strides, unit column stride), q bf16 [heads, hd] contiguous, pad uint8 /
+    bool [B, S] (non-zero = masked; unit column stride) or None.  Returns (out bf16 [B, heads * hd], p fp32 [B, heads, S])."""
+    heads, hd = q.shape
+    _req(q, "q", torch.bfloat16)
+    B, S, ld, bs = _attn_pool_kv(k, v, heads, hd)
+    ld_pad = 0
+    if pad is not None:
+        if pad.dtype == torch.bool:
+            pad = pad.view(torch.uint8)
+        if not pad.is_cuda or pad.dtype != torch.uint8 or tuple(pad.shape) != (B, S) or (S > 1 and pad.stride(1) != 1):
+            raise RuntimeError("attn_pool_fwd: pad must be a uint8 / bool CUDA(HIP) tensor [B, S] with unit column stride")
+        ld_pad = pad.stride(0) if B > 1 else max(pad.stride(0), S)
+    if out is None:
+        out = torch.empty(B, heads * hd, dtype=torch.bfloat16, device=k.device)
+    if p is None:
+        p = torch.empty(B, heads, S, dtype=torch.float32, device=k.device)
+    assert out.is_contiguous() and out.dtype == torch.bfloat16 and tuple(out.shape) == (B, heads * hd)
+    assert p.is_contiguous() and p.dtype == torch.float32 and p.numel() == B * heads * S
+    _check(lib().op_attn_pool_fwd(ptr(k), ptr(v), ld, bs, ptr(q), ptr(pad), ld_pad, ptr(out), ptr(p), B, S, heads, hd, stream()),
+           "op_attn_pool_fwd")
+    return out, p
+
+
+def attn_pool_bwd(dout, k, v, q, p, dk=None, dv=None, dq_part=None):
+    """op_attn_pool_bwd: returns (dk, dv bf16 [B, S, heads * hd], dq_part fp32 [B, heads * hd]); the caller sums dq_part over B.
+    dk / dv may be given as views with their own (shared) strides."""
+    heads, hd = q.shape
+    _req(q, "q", torch.bfloat16)
+    _req(dout, "dout", torch.bfloat16)
+    _req(p, "p", torch.float32)
+    B, S, ld, bs = _attn_pool_kv(k, v, heads, hd)
+    if dk is None:
+        dk = torch.empty(B, S, heads * hd, dtype=torch.bfloat16, device=k.device)
+        dv = torch.empty(B, S, heads * hd, dtype=torch.bfloat16, device=k.device)
+    _, _, ldg, bsg = _attn_pool_kv(dk, dv, heads, hd)
+    assert dk.shape == k.shape and tuple(dout.shape) == (B, heads * hd) and p.numel() == B * heads * S
+    if dq_part is None:
+        dq_part = torch.empty(B, heads * hd, dtype=torch.float32, device=k.device)
+    assert dq_part.is_contiguous() and dq_part.dtype == torch.float32 and tuple(dq_part.shape) == (B, heads * hd)
+    _check(lib().op_attn_pool_bwd(ptr(dout), ptr(k), ptr(v), ld, bs, ptr(q), ptr(p), ptr(dk), ptr(dv), ldg, bsg, ptr(dq_part), B, S, heads,
+                                  hd, stream()), "op_attn_pool_bwd")
+    return dk, dv, dq_part
 
 
 def mfma_rate_probe(seconds=1.0, waves_per_cu=8, data="normal", device=None):

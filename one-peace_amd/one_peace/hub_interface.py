@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from ..unify_model_config import one_peace_encoder_config
+from .one_peace_classify import OnePeaceClassifyModel
 from .one_peace_retrieval import OnePeaceRetrievalModel
 
 _DTYPES = {"float32": torch.float32, "fp32": torch.float32, "fp16": torch.float16, "float16": torch.float16,
@@ -41,8 +42,14 @@ def _cfg_get(tree, key, default=None):
     return getattr(tree, key, default)
 
 
-def build_from_checkpoint_cfg(model_cfg, head_type="vl", patch_image_size=256, vocab_size=50265):
-    """Build the retrieval model from the `cfg.model` tree of a reference checkpoint (dict / namespace / omegaconf)."""
+_CLASSIFY_FIELDS = (("head_scale_ratio", 1), ("use_pooler", False), ("pooler_dropout", 0.0), ("attn_pooling", False),
+                    ("use_image_features", False), ("freeze_finetune_updates", 0))
+
+
+def build_from_checkpoint_cfg(model_cfg, head_type="vl", patch_image_size=256, vocab_size=50265, model_type="one_peace_retrieval",
+                              num_classes=None, use_two_images=False):
+    """Build the model from the `cfg.model` tree of a reference checkpoint (dict / namespace / omegaconf): the retrieval model, or
+    with model_type="one_peace_classify" the fine-tuning model (num_classes / use_two_images are the task's, as in its build_model)."""
     enc = _cfg_get(model_cfg, "encoder")
     kw = {}
     for k in ("embed_dim", "ffn_embed_dim", "layers", "attention_heads", "drop_path_rate", "layer_scale_init_value"):
@@ -63,17 +70,26 @@ def build_from_checkpoint_cfg(model_cfg, head_type="vl", patch_image_size=256, v
                 if v is not None:
                     setattr(tgt, f, v)
     cfg_enc.image_adapter.rel_bucket_size = patch_image_size // 16
+    if model_type == "one_peace_classify":
+        cfg = SimpleNamespace(encoder=cfg_enc, **{k: type(d)(_cfg_get(model_cfg, k, d)) for k, d in _CLASSIFY_FIELDS})
+        return OnePeaceClassifyModel(cfg, _Dictionary(vocab_size), head_type, num_classes=num_classes, use_two_images=use_two_images)
+    if model_type != "one_peace_retrieval":
+        raise NotImplementedError("from_pretrained: model_type %r (one_peace_retrieval or one_peace_classify)" % (model_type,))
     cfg = SimpleNamespace(encoder=cfg_enc, copy_rel_pos_table=bool(_cfg_get(model_cfg, "copy_rel_pos_table", False)))
     return OnePeaceRetrievalModel(cfg, _Dictionary(vocab_size), head_type)
 
 
 def from_pretrained(model_name_or_path, model_type="one_peace_retrieval", device="cuda", dtype="float32",
-                    download_root=None, head_type="vl", patch_image_size=256):
+                    download_root=None, head_type="vl", patch_image_size=256, num_classes=None, use_two_images=False):
     """hub_interface.py:53-73.  `model_name_or_path` must be a local checkpoint file ({"cfg": {"model": ...}, "model":
-    state_dict}); downloading by name needs network access and the reference's URL table."""
+    state_dict}); downloading by name needs network access and the reference's URL table.  model_type="one_peace_classify" builds
+    the fine-tuning model; head_type, num_classes and use_two_images are what the reference reads from the checkpoint's task."""
     ckpt = torch.load(model_name_or_path, map_location="cpu", weights_only=False)
     model_cfg = _cfg_get(_cfg_get(ckpt, "cfg"), "model")
-    model = build_from_checkpoint_cfg(model_cfg, head_type=head_type, patch_image_size=patch_image_size)
+    embed = ckpt["model"].get("encoder_wrapper.text_adapter.embed_tokens.weight")  # the dictionary's size, where there is a text tower
+    model = build_from_checkpoint_cfg(model_cfg, head_type=head_type, patch_image_size=patch_image_size, model_type=model_type,
+                                      num_classes=num_classes, use_two_images=use_two_images,
+                                      vocab_size=embed.shape[0] if embed is not None else 50265)
     model.load_state_dict(ckpt["model"], strict=True)
     return OnePeaceHubInterface(model, device=device, dtype=dtype)
 
@@ -198,6 +214,10 @@ class OnePeaceHubInterface:
         return graphs[tag](**kw)
 
     def _eager(self, tag, **kw):
+        if isinstance(self.model, OnePeaceClassifyModel):
+            # hub_interface.py:206-225: the classify model is called without encoder_type and returns its logits.  (The reference's
+            # extract_text_features forgets the `return` for this model type and yields None; the logits are returned here.)
+            return self.model(**kw)
         if tag == "vl":
             tf, _, _ = self.model.encoder_wrapper(encoder_type="vl", **kw)
             return tf[:, 0, :]

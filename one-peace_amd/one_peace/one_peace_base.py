@@ -1,6 +1,6 @@
 """Mirror of one_peace/models/one_peace/one_peace_base.py: ``ModelWrapper`` (adapters + shared encoder, routing by
-``encoder_type``), the registered base model and the parameter initialiser.  Fine-tune heads
-(MultiheadAttentionPooling / OnePeaceClassifyHead) are out of the hot-path scope."""
+``encoder_type``), the fine-tuning head (MultiheadAttentionPooling over ops.attention_pool, OnePeaceClassifyHead), the registered
+base model and the parameter initialiser."""
 import logging
 from typing import Optional
 
@@ -10,7 +10,8 @@ import torch.nn as nn
 from ..adapter.audio import AudioAdapter
 from ..adapter.image import ImageAdapter
 from ..adapter.text import TextAdapter
-from ..components import trunc_normal_
+from .. import ops
+from ..components import LayerNorm, Linear, trunc_normal_
 from ..registry import BaseFairseqModel, register_model
 from ..transformer.transformer_encoder import TransformerEncoder
 from ..unify_model_config import UnifyModelConfig
@@ -85,6 +86,60 @@ def _wrapper_forward_multi(self, src_tokens=None, src_images=None, src_audios=No
 
 
 ModelWrapper.forward_multi = _wrapper_forward_multi
+
+
+class MultiheadAttentionPooling(nn.Module):
+    """one_peace_base.py:132-172: one learned query per head attends over the tokens.  The projections are GEMMs through
+    components.Linear; lines 157 and 160-170 are ops.attention_pool (the HIP kernel pair for bf16 device tensors -- k and v are the two
+    [B, S, H] outputs of the projections, read in place -- and the reference's torch ops otherwise)."""
+
+    def __init__(self, embed_dim, num_heads):
+        super().__init__()
+        self.embed_dim, self.num_heads, self.head_dim = embed_dim, num_heads, embed_dim // num_heads
+        self.k_proj = Linear(embed_dim, embed_dim, bias=False)
+        self.v_proj = Linear(embed_dim, embed_dim, bias=True)
+        self.out_proj = Linear(embed_dim, embed_dim, bias=True)
+        self.q = nn.Parameter(torch.zeros(1, 1, self.num_heads, self.head_dim))
+        trunc_normal_(self.q)
+
+    def forward(self, x, key_padding_mask=None):
+        """x: B x S x C; key_padding_mask: B x S, non-zero = pad."""
+        attn = ops.attention_pool(self.k_proj(x), self.v_proj(x), self.q, key_padding_mask)
+        return self.out_proj(attn)
+
+
+class OnePeaceClassifyHead(nn.Module):
+    """one_peace_base.py:175-235, same parameter names: norm, attn_pooling_func.{q, k_proj, v_proj, out_proj}, pooler.1,
+    classifier.{0, 1, 3}."""
+
+    def __init__(self, attn_pooling, use_pooler, pooler_dropout, input_dim, num_heads, head_scale_ratio, num_classes,
+                 use_two_images=False):
+        super().__init__()
+        self.attn_pooling = attn_pooling
+        self.norm = LayerNorm(input_dim)
+        self.attn_pooling_func = MultiheadAttentionPooling(input_dim, num_heads) if attn_pooling else None
+        if use_pooler:
+            self.pooler = nn.Sequential(nn.Dropout(p=pooler_dropout), Linear(input_dim, input_dim), nn.Tanh(),
+                                        nn.Dropout(p=pooler_dropout))
+        else:
+            self.pooler = None
+        classifier_input_dim = input_dim * 2 if use_two_images else input_dim
+        inner_dim = int(input_dim * head_scale_ratio)
+        self.classifier = nn.Sequential(Linear(classifier_input_dim, inner_dim), LayerNorm(inner_dim), nn.GELU(),
+                                        Linear(inner_dim, num_classes))
+
+    def forward_features(self, features, padding_masks):
+        if self.attn_pooling:  # over tokens 1 ... with the mask's columns 1 ...: the slices are views, the kernels read them in place
+            x = self.norm(self.attn_pooling_func(features[:, 1:, :], padding_masks[:, 1:]))
+        else:
+            x = features[:, 0, :]
+        return self.pooler(x) if self.pooler is not None else x
+
+    def forward(self, features_1, features_2, padding_masks):
+        x = self.forward_features(features_1, padding_masks)
+        if features_2 is not None:
+            x = torch.cat([x, self.forward_features(features_2, padding_masks)], dim=1)
+        return self.classifier(x)
 
 
 @register_model("one_peace_base", dataclass=UnifyModelConfig)

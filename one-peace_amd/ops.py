@@ -1902,3 +1902,70 @@ def box_loss(logits, targets):
     if loss_hip_eligible(logits):
         return BoxLossFn.apply(logits, targets.to(logits.device, torch.float32).contiguous())
     return box_loss_torch(logits, targets)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# fine-tuning head: single-query attention pooling (one_peace_base.py:154-170 between the projections; csrc/attnpool.hip)
+# --------------------------------------------------------------------------------------------------------------
+def attention_pool_torch(k, v, q, key_padding_mask=None):
+    """one_peace_base.py:154-170 with k = k_proj(x), v = v_proj(x) given as [B, S, H]: the same torch ops in the same order and the same
+    dtypes (bmm at the input dtype, masked_fill_ with -inf, softmax(dtype=float32), type_as, bmm), on the reference's own layout
+    (time-major [S, B * heads, hd] viewed batch-major).  No 1 / sqrt(hd) factor.  key_padding_mask None: nothing is masked."""
+    B, S, H = k.shape
+    heads, hd = q.shape[-2], q.shape[-1]
+    q = q.reshape(1, 1, heads, hd).expand(1, B, -1, -1).reshape(1, B * heads, hd).transpose(0, 1)
+    k = k.transpose(0, 1).contiguous().view(S, B * heads, hd).transpose(0, 1)
+    v = v.transpose(0, 1).contiguous().view(S, B * heads, hd).transpose(0, 1)
+    attn_weights = torch.bmm(q, k.transpose(1, 2))
+    attn_weights = attn_weights.view(B, heads, 1, S)
+    if key_padding_mask is not None:
+        key_padding_mask = key_padding_mask.to(torch.bool).view(B, 1, 1, S).contiguous()
+        attn_weights.masked_fill_(key_padding_mask.expand(B, heads, 1, S), -math.inf)
+    attn_weights_float = F.softmax(attn_weights, dim=-1, dtype=torch.float32)  # fairseq's utils.softmax
+    attn_probs = attn_weights_float.type_as(attn_weights)
+    attn_probs = attn_probs.view(B * heads, 1, S)
+    attn = torch.bmm(attn_probs, v)
+    return attn.reshape(B, H)
+
+
+class AttentionPoolFn(torch.autograd.Function):
+    """op_attn_pool_fwd / op_attn_pool_bwd; the fp32 probabilities [B, heads, S] are kept for the backward, the per-sample partials of
+    the query gradient are summed over the batch by one torch.sum (fixed order, no atomics)."""
+
+    @staticmethod
+    def forward(ctx, k, v, q, pad):
+        out, p = hip.attn_pool_fwd(k, v, q, pad)
+        ctx.save_for_backward(k, v, q, p)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        k, v, q, p = ctx.saved_tensors
+        dk, dv, dq_part = hip.attn_pool_bwd(dout.contiguous(), k, v, q, p)
+        return dk, dv, torch.sum(dq_part, dim=0).view(q.shape).to(q.dtype), None
+
+
+def attention_pool(k, v, q, key_padding_mask=None):
+    """[B, H] = the heads' softmax(q_h . k_s) weighted sums of v over the unmasked keys (no 1 / sqrt(hd)): MultiheadAttentionPooling
+    between its projections.  k, v: [B, S, H]; q: [heads, hd] or the reference's parameter [1, 1, heads, hd]; key_padding_mask: [B, S],
+    non-zero = pad.  bf16 CUDA tensors inside the kernels' limits (hip.attn_pool_supported) run op_attn_pool_fwd / _bwd, where a masked
+    key is skipped (its k / v rows never read, zero gradient rows); everything else -- CPU, fp32, fp16, hd % 8 != 0, hd > 128,
+    S > 4096, unaligned strides -- runs attention_pool_torch.  A sample with every key masked gives NaN either way."""
+    heads, hd = q.shape[-2], q.shape[-1]
+    if k.dim() != 3 or k.shape != v.shape or k.shape[2] != heads * hd or q.numel() != heads * hd:
+        raise ValueError("attention_pool: k %s, v %s must be [B, S, heads * hd] for q %s" % (tuple(k.shape), tuple(v.shape), tuple(q.shape)))
+    if key_padding_mask is not None and tuple(key_padding_mask.shape) != tuple(k.shape[:2]):
+        raise ValueError("attention_pool: key_padding_mask %s does not match k %s" % (tuple(key_padding_mask.shape), tuple(k.shape)))
+    if hip_eligible(k) and hip_eligible(v) and hip_eligible(q):
+        if k.stride() != v.stride() and k.is_contiguous():
+            v = v.contiguous()
+        if hip.attn_pool_supported(k, v, heads, hd):
+            pad = key_padding_mask
+            if pad is not None:
+                pad = pad.to(k.device)
+                if pad.dtype not in (torch.bool, torch.uint8):
+                    pad = pad != 0
+                if pad.shape[1] > 1 and pad.stride(1) != 1:
+                    pad = pad.contiguous()
+            return AttentionPoolFn.apply(k, v, q.reshape(heads, hd).contiguous(), pad)
+    return attention_pool_torch(k, v, q, key_padding_mask)
