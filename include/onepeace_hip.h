@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* ---- library ------------------------------------------------------------------------------------------------ */
-int op_abi_version(void); /* 2: per-call `tune` words replaced the process-wide knob setters; 3: op_gemm_nt_grouped, op_ln_geglu_fwd, ldd / ldh of op_ln_geglu_bwd, `out` of op_attn_bwd; 4: op_gemm_tn_grouped; 5: op_probe_mfma_rate, op_rows_gather / op_rows_merge, 16-byte rule of op_gemm_tn_grouped's C; 6: the op_probe_* entry points left for libonepeace_probe.so (include/onepeace_probe.h), op_gemm_nt_grouped answers OP_ENOTSUP for the GeGLU epilogue, op_gemm_tn_grouped_plan takes the workgroup count and tune word; 7: W / ldw / rowdot of op_gemm_tn_grouped, g0 of op_resid_bwd, op_gamma_grad_finish, op_gemm_nt_batched, op_audio_conv1_ln_gelu_fwd / _bwd; 8: the layer-scale gradient without a division -- rscale of op_gemm_tn_grouped, op_transpose_scaled + the scale member of the op_transpose_batched descriptor, op_resid_bwd leaves gamma out of dbranch when g0 is asked for, op_gamma_grad_finish lost its gamma argument; rowdot is a [N / 128][M] matrix of partial sums written once each (no atomics); 9: row tables -- a residual branch that runs on the samples stochastic depth keeps reads and writes the FULL activation matrix through op_rows_map's table instead of through packed copies: x_rows of op_layernorm_fwd / op_layernorm_bwd, dout_rows of op_resid_bwd, resid_rows / resid_rows_total of op_gemm_nt and op_gemm_nt_grouped, op_rows_merge without `upd` copies the dropped samples' rows only; op_prof_reserve; 10: run-to-run identical gradients -- op_relpos_bias_bwd sums the table gradient in a fixed order from pair lists instead of scattering with atomics, op_relpos_bias_bwd_ids became op_relpos_bias_fold_ids, the separate dBias kernel of op_attn_bwd adds into one slab per batch chunk; (still 10, additive) op_live_ktiles + op_gemm_tn_grouped_lists: the weight gradients skip the K-tiles of samples stochastic depth dropped */
+int op_abi_version(void); /* 2: per-call `tune` words replaced the process-wide knob setters; 3: op_gemm_nt_grouped, op_ln_geglu_fwd, ldd / ldh of op_ln_geglu_bwd, `out` of op_attn_bwd; 4: op_gemm_tn_grouped; 5: op_probe_mfma_rate, op_rows_gather / op_rows_merge, 16-byte rule of op_gemm_tn_grouped's C; 6: the op_probe_* entry points left for libonepeace_probe.so (include/onepeace_probe.h), op_gemm_nt_grouped answers OP_ENOTSUP for the GeGLU epilogue, op_gemm_tn_grouped_plan takes the workgroup count and tune word; 7: W / ldw / rowdot of op_gemm_tn_grouped, g0 of op_resid_bwd, op_gamma_grad_finish, op_gemm_nt_batched, op_audio_conv1_ln_gelu_fwd / _bwd; 8: the layer-scale gradient without a division -- rscale of op_gemm_tn_grouped, op_transpose_scaled + the scale member of the op_transpose_batched descriptor, op_resid_bwd leaves gamma out of dbranch when g0 is asked for, op_gamma_grad_finish lost its gamma argument; rowdot is a [N / 128][M] matrix of partial sums written once each (no atomics); 9: row tables -- a residual branch that runs on the samples stochastic depth keeps reads and writes the FULL activation matrix through op_rows_map's table instead of through packed copies: x_rows of op_layernorm_fwd / op_layernorm_bwd, dout_rows of op_resid_bwd, resid_rows / resid_rows_total of op_gemm_nt and op_gemm_nt_grouped, op_rows_merge without `upd` copies the dropped samples' rows only; op_prof_reserve; 10: run-to-run identical gradients -- op_relpos_bias_bwd sums the table gradient in a fixed order from pair lists instead of scattering with atomics, op_relpos_bias_bwd_ids became op_relpos_bias_fold_ids, the separate dBias kernel of op_attn_bwd adds into one slab per batch chunk; (still 10, additive) op_live_ktiles + op_gemm_tn_grouped_lists: the weight gradients skip the K-tiles of samples stochastic depth dropped; (still 10, additive) op_live_mwindows + op_gemm_nt_grouped_windows: the input gradients skip their row blocks */
 const char* op_last_error(void);
 
 /* Live per-kernel-family timing with HIP events recorded on the launch stream (used by bench.py's `roofline`).
@@ -171,6 +171,31 @@ int op_gemm_tn_grouped_lists(int64_t nprob, const void* const* A, const int64_t*
  * Additive: op_abi_version() stays 10. */
 int op_live_ktiles(int64_t nseg, const float* const* ps, const int64_t* row0, const int64_t* S, const int64_t* B, int64_t nprob,
                    const int64_t* prob_row0, const int64_t* prob_rows, int32_t* const* ktiles, int32_t* const* n_ktiles, void* stream);
+/* Window lists for the INPUT-gradient GEMMs of such a branch, and the zero rows those launches leave out: one launch, no host
+ * synchronisation.  Segments as in op_live_ktiles, plus ps_stride[i] (sample b has the multiplier ps_i[b * ps_stride[i]]: a per-row
+ * vector serves with ps_stride = S) and wps[i]: > 0 -- every sample with ps != 0 is listed as wps[i] windows of 256
+ * rows from its first row on (odd[i] != 0, for S = 256 n + 1: and the last row of EVERY sample in strided windows of 256 samples);
+ * 0 -- the aligned 256-row tiles of the segment that hold a row of such a sample.  seg_list / seg_prob /
+ * seg_base (HOST, nseg x 2): the up to two lists a segment feeds (-1: none), the problem index its entries carry there and the row
+ * of the row matrix at which that problem's operand starts (<= row0_i); an entry is two words, prob << 28 | (row - base) and
+ * rows << 16 | row stride.  windows[l] (DEVICE int32 [2 * max_windows[l]]) and n_windows[l] (DEVICE int32) for nlist <= 4 lists, filled segment by segment, ascending.  out (nout <= 4,
+ * may be 0): bf16 matrices of out_rows[o] rows parallel to the row matrix (row stride out_ld[o], out_cols[o] columns, both % 8 == 0);
+ * the rows of every sample / tile that is not listed are set to +0 in each of them.  Additive: op_abi_version() stays 10. */
+int op_live_mwindows(int64_t nseg, const float* const* ps, const int64_t* ps_stride, const int64_t* row0, const int64_t* S, const int64_t* B,
+                     const int64_t* wps, const int64_t* odd, const int64_t* seg_list, const int64_t* seg_prob, const int64_t* seg_base, int64_t nlist,
+                     int32_t* const* windows,
+                     int32_t* const* n_windows, const int64_t* max_windows, int64_t nout, void* const* out, const int64_t* out_ld,
+                     const int64_t* out_cols, const int64_t* out_rows, void* stream);
+/* op_gemm_nt_grouped's plain form (no bias) over a window list: computes the rows r, r + s, ... (n of them, n <= 256) of C_p for the
+ * two-word entries (prob << 28 | r, n << 16 | s) of windows[0 .. *n_windows) (DEVICE int32 [2 * max_windows], 8-byte aligned, written on the device
+ * before the launch -- op_live_mwindows --, never read by the host; max_windows sizes the grid) and writes no other row.  s = 1: r is
+ * any row of the problem; blocks may overlap (the same bits twice) and may pass the problem's end (fetched as zeros, not stored).
+ * s > 1 (<= max_row_stride, with max_row_stride * lda and * ldc < 2^23): one row of each of n consecutive s-row samples.  B: ONE weight per problem.  Every listed block has the bits
+ * of the dense launch: same operands, same K order.  A non-finite operand in a row that is not listed is not multiplied (the dense
+ * launch gives NaN there).  OP_ENOTSUP as op_gemm_nt_grouped.  Additive: op_abi_version() stays 10. */
+int op_gemm_nt_grouped_windows(int64_t nprob, const void* const* A, const int64_t* M, int64_t lda, const void* const* B, int64_t ldb,
+                               void* const* C, int64_t ldc, int64_t N, int64_t K, const int32_t* windows, const int32_t* n_windows,
+                               int64_t max_windows, int64_t max_row_stride, int64_t tune, void* stream);
 /* `tune` (op_gemm_nt, op_gemm_tn, op_gemm_plan): per-call tuning word, 0 = what production uses.  The library keeps NO tuning
  * state, so every entry point is a pure function of its arguments; tests and tools select a kernel flavour with the call:
  * bits 0-1 tile (0 auto: a cost model picks 128x128 or 256x256 tiles, K-splits and the tail-rows split; 1 force 128x128;

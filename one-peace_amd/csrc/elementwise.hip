@@ -818,6 +818,102 @@ __global__ __launch_bounds__(256) void live_ktiles_kernel(const LiveTilesArgs a)
   if (tid == 0) *a.prob[blockIdx.x].count = base;
 }
 
+// Window lists for the INPUT-gradient GEMMs of such a branch (consumer: op_gemm_nt_grouped_windows), and the zero rows those launches
+// no longer write.  A segment is cut into UNITS: wps > 0 -- a unit is a sample, and a kept sample (ps != 0) is listed as wps windows of
+// 256 rows from its first row on (odd: they leave out each sample's last row, and the rows S - 1, 2 S - 1, ... of ALL samples are listed
+// as strided windows, 256 samples each); wps == 0 -- a unit is an aligned 256-row tile of the segment, listed when one of its rows
+// belongs to a kept sample.  A segment feeds up to two lists (the launch of its own rows and a grouped launch, with its problem index there); an
+// entry is two words: prob << 28 | (row - base), rows << 16 | row stride.  Grid: x = unit (all segments, then one workgroup per LIST that builds it: ordered ballot
+// compaction, segment by segment), y = MW_PIECE-row piece of the unit: the pieces of a unit that is NOT listed write +0 into their rows of
+// every output matrix (16-byte stores; the host checks cols % 8 == 0 and ld % 8 == 0).
+constexpr int MW_MAX_SEG = 4, MW_MAX_OUT = 4, MW_MAX_LIST = 4;
+constexpr int MW_PIECE = 16;  // rows a workgroup zero-fills: 64-row pieces left one workgroup per CU busy (1.4 TB/s on the FFN outputs)
+struct MWindowsArgs {
+  int nseg, nout, nlist, nunits;
+  struct { const float* ps; int64_t row0; int S, B, wps, odd, pstride, unit0, units; int list[2], prob[2]; int64_t base[2]; } seg[MW_MAX_SEG];
+  struct { bf16_t* ptr; int64_t ld; int cols; } out[MW_MAX_OUT];
+  struct { int* list; int* count; } lists[MW_MAX_LIST];
+};
+
+template <class Seg>
+__device__ __forceinline__ bool mw_unit_live(const Seg& sg, int u) {
+  if (sg.ps == nullptr) return true;
+  if (sg.wps > 0) return sg.ps[(int64_t)u * sg.pstride] != 0.f;
+  const int64_t lo = (int64_t)u * 256, hi = min(lo + 256, (int64_t)sg.S * sg.B);
+  bool live = false;
+  for (int sm = (int)(lo / sg.S); sm <= (int)((hi - 1) / sg.S); ++sm) live = live || sg.ps[(int64_t)sm * sg.pstride] != 0.f;
+  return live;
+}
+
+__global__ __launch_bounds__(256) void live_mwindows_kernel(const MWindowsArgs a) {
+  __shared__ int wave_n[4];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if ((int)blockIdx.x >= a.nunits) {  // ---- list blockIdx.x - nunits ----
+    if (blockIdx.y != 0) return;
+    {
+      const int l = (int)blockIdx.x - a.nunits;
+      int base = 0;  // (uniform) entries of list l so far
+      for (int i = 0; i < a.nseg; ++i) {
+        for (int k = 0; k < 2; ++k) {
+          if (a.seg[i].list[k] != l) continue;
+          const int per = a.seg[i].wps > 0 ? a.seg[i].wps : 1;
+          for (int c = 0; c < a.seg[i].units; c += 256) {
+            const int u = c + tid;
+            const bool live = u < a.seg[i].units && mw_unit_live(a.seg[i], u);
+            const unsigned long long m = __ballot(live);
+            if (lane == 0) wave_n[wid] = __popcll(m);
+            __syncthreads();
+            int before = base;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+              if (w < wid) before += wave_n[w] * per;
+              base += wave_n[w] * per;
+            }
+            if (live) {
+              const int64_t first = a.seg[i].row0 - a.seg[i].base[k] + (int64_t)u * (a.seg[i].wps > 0 ? a.seg[i].S : 256);
+              int* dst = a.lists[l].list + 2 * (before + __popcll(m & ((1ull << lane) - 1ull)) * per);
+              for (int w = 0; w < per; ++w) {
+                dst[2 * w] = (a.seg[i].prob[k] << 28) | (int)(first + w * 256);
+                dst[2 * w + 1] = (256 << 16) | 1;
+              }
+            }
+            __syncthreads();
+          }
+          if (a.seg[i].odd) {  // the last row of EVERY sample (a dropped one: zeros in, zeros out), 256 samples to a window
+            const int nw = (a.seg[i].B + 255) / 256;
+            if (tid < nw) {
+              int* dst = a.lists[l].list + 2 * (base + tid);
+              dst[0] = (a.seg[i].prob[k] << 28) | (int)(a.seg[i].row0 - a.seg[i].base[k] + (int64_t)tid * 256 * a.seg[i].S + a.seg[i].S - 1);
+              dst[1] = (min(256, a.seg[i].B - tid * 256) << 16) | a.seg[i].S;
+            }
+            base += nw;
+          }
+        }
+      }
+      if (tid == 0) *a.lists[l].count = base;
+    }
+    return;
+  }
+  // ---- zero rows: unit blockIdx.x of segment i, rows [blockIdx.y * MW_PIECE, + MW_PIECE) of it ----
+  int i = 0;
+#pragma unroll
+  for (int j = 1; j < MW_MAX_SEG; ++j)
+    if (j < a.nseg && (int)blockIdx.x >= a.seg[j].unit0) i = j;
+  const int u = (int)blockIdx.x - a.seg[i].unit0;
+  const int64_t seg_rows = (int64_t)a.seg[i].S * a.seg[i].B;
+  const int64_t ubeg = (int64_t)u * (a.seg[i].wps > 0 ? a.seg[i].S : 256);
+  const int64_t uend = min(ubeg + (a.seg[i].wps > 0 ? a.seg[i].S : 256), seg_rows);
+  const int64_t r0 = ubeg + (int64_t)blockIdx.y * MW_PIECE, r1 = min(r0 + MW_PIECE, uend);
+  if (r0 >= r1 || mw_unit_live(a.seg[i], u)) return;
+  const int nrows = (int)(r1 - r0);
+  for (int o = 0; o < a.nout; ++o) {
+    const int c8 = a.out[o].cols >> 3;
+    bf16_t* base = a.out[o].ptr + (a.seg[i].row0 + r0) * a.out[o].ld;
+    for (int r = wid; r < nrows; r += 4)  // a wave per row: 1 KiB contiguous per store instruction
+      for (int c = lane; c < c8; c += 64) *reinterpret_cast<uint4*>(base + (int64_t)r * a.out[o].ld + c * 8) = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1267,6 +1363,70 @@ int op_live_ktiles(int64_t nseg, const float* const* ps, const int64_t* row0, co
     a.prob[p].row0 = prob_row0[p]; a.prob[p].ntiles = (int)(prob_rows[p] / 64); a.prob[p].list = ktiles[p]; a.prob[p].count = n_ktiles[p];
   }
   hipLaunchKernelGGL(live_ktiles_kernel, dim3((int)nprob), dim3(256), 0, (hipStream_t)stream, a);
+  OP_LAUNCH_CHECK();
+  return OP_OK;
+}
+
+// (additive: op_abi_version() stays 10) Window lists for the input-gradient GEMMs of a residual branch (op_gemm_nt_grouped_windows) and the zero rows they leave
+// out, ONE launch, no host synchronisation (see live_mwindows_kernel).  Segments as in op_live_ktiles (HOST arrays of nseg <= 4 entries),
+// plus per segment ps_stride (sample b has the multiplier ps[b * ps_stride]: a per-row vector serves with ps_stride = S) and wps: > 0 -- every kept sample is listed as wps windows of 256 rows from its first row on (the caller picks this
+// where a sample nearly fills them; odd[i] != 0: and every sample's LAST row, kept or not, is listed in strided windows of 256 samples
+// -- for S = 256 n + 1); 0 -- the aligned 256-row tiles of the segment that hold a row of a kept sample.  seg_list /
+// seg_prob / seg_base (nseg x 2): the up to two lists a segment feeds (-1: none), the problem index its entries carry there and the
+// row of the row matrix at which that problem's operand starts (<= row0; an entry is two words, prob << 28 | row - base and rows << 16 | row stride).  Lists (HOST arrays of
+// nlist <= 4): windows[l] DEVICE int32 [2 * max_windows[l]], n_windows[l] DEVICE int32 [1]; the order is segment by segment, ascending.
+// Outputs (nout <= 4, may be 0): bf16 matrices of out_rows[o] rows PARALLEL to the row matrix (row stride out_ld[o], out_cols[o]
+// columns, both % 8 == 0); the rows of every unit (sample / tile) that is not listed are set to +0 in all of them.  A row that only a
+// neighbour's window reaches is zeroed here and written again by the GEMM, which runs later on the stream.
+int op_live_mwindows(int64_t nseg, const float* const* ps, const int64_t* ps_stride, const int64_t* row0, const int64_t* S, const int64_t* B,
+                     const int64_t* wps, const int64_t* odd, const int64_t* seg_list, const int64_t* seg_prob, const int64_t* seg_base, int64_t nlist,
+                     int32_t* const* windows,
+                     int32_t* const* n_windows, const int64_t* max_windows, int64_t nout, void* const* out, const int64_t* out_ld,
+                     const int64_t* out_cols, const int64_t* out_rows, void* stream) {
+  OP_CHECK_ARG(nseg >= 1 && nseg <= MW_MAX_SEG && nlist >= 1 && nlist <= MW_MAX_LIST && nout >= 0 && nout <= MW_MAX_OUT,
+               "live_mwindows: %lld segments (1 ... %d), %lld lists (1 ... %d), %lld outputs (0 ... %d)", (long long)nseg, MW_MAX_SEG,
+               (long long)nlist, MW_MAX_LIST, (long long)nout, MW_MAX_OUT);
+  OP_CHECK_ARG(ps && ps_stride && row0 && S && B && wps && odd && seg_list && seg_prob && seg_base && windows && n_windows && max_windows &&
+               (nout == 0 || (out && out_ld && out_cols && out_rows)), "live_mwindows: null pointer");
+  MWindowsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.nseg = (int)nseg; a.nout = (int)nout; a.nlist = (int)nlist;
+  int64_t need[MW_MAX_LIST] = {0, 0, 0, 0}, last_row = 0, unit_rows = 1;
+  int units = 0;
+  for (int i = 0; i < (int)nseg; ++i) {
+    OP_CHECK_ARG(row0[i] >= 0 && S[i] >= 1 && B[i] >= 1 && S[i] * B[i] < ((int64_t)1 << 27) && row0[i] < ((int64_t)1 << 40) && wps[i] >= 0 && ps_stride[i] >= 1 && ps_stride[i] < ((int64_t)1 << 31) &&
+                 wps[i] <= 64 && (wps[i] == 0 || S[i] <= ((int64_t)1 << 19)) &&
+                 (odd[i] == 0 || (wps[i] > 0 && S[i] < 65536 && B[i] <= 65536)), "live_mwindows: bad segment %d", i);
+    auto& sg = a.seg[i];
+    sg.ps = ps[i]; sg.row0 = row0[i]; sg.S = (int)S[i]; sg.B = (int)B[i]; sg.wps = (int)wps[i]; sg.odd = odd[i] != 0; sg.pstride = (int)ps_stride[i];
+    sg.unit0 = units;
+    sg.units = sg.wps > 0 ? sg.B : (int)((S[i] * B[i] + 255) / 256);
+    units += sg.units;
+    if (row0[i] + S[i] * B[i] > last_row) last_row = row0[i] + S[i] * B[i];
+    if ((sg.wps > 0 ? S[i] : 256) > unit_rows) unit_rows = sg.wps > 0 ? S[i] : 256;
+    for (int k = 0; k < 2; ++k) {
+      const int64_t l = seg_list[i * 2 + k];
+      sg.list[k] = (int)l;
+      if (l < 0) { sg.list[k] = -1; continue; }
+      OP_CHECK_ARG(l < nlist && seg_prob[i * 2 + k] >= 0 && seg_prob[i * 2 + k] <= 2 && seg_base[i * 2 + k] >= 0 &&
+                   seg_base[i * 2 + k] <= row0[i] && row0[i] - seg_base[i * 2 + k] + S[i] * B[i] + 256 * wps[i] < ((int64_t)1 << 28),
+                   "live_mwindows: segment %d: bad list reference %d", i, k);
+      sg.prob[k] = (int)seg_prob[i * 2 + k]; sg.base[k] = seg_base[i * 2 + k];
+      need[l] += (int64_t)sg.units * (sg.wps > 0 ? sg.wps : 1) + (sg.odd ? (sg.B + 255) / 256 : 0);
+    }
+  }
+  a.nunits = units;
+  for (int l = 0; l < (int)nlist; ++l) {
+    OP_CHECK_ARG(windows[l] && n_windows[l] && max_windows[l] >= need[l], "live_mwindows: list %d: null, or room for %lld entries (%lld needed)", l,
+                 (long long)max_windows[l], (long long)need[l]);
+    a.lists[l].list = windows[l]; a.lists[l].count = n_windows[l];
+  }
+  for (int o = 0; o < (int)nout; ++o) {
+    OP_CHECK_ARG(out[o] && ((uintptr_t)out[o] & 15) == 0 && out_cols[o] >= 8 && out_cols[o] % 8 == 0 && out_ld[o] % 8 == 0 && out_ld[o] >= out_cols[o] && out_rows[o] >= last_row &&
+                 out_cols[o] < ((int64_t)1 << 31), "live_mwindows: output %d: null or not 16-byte aligned, cols / ld %% 8, or fewer than %lld rows", o, (long long)last_row);
+    a.out[o].ptr = (bf16_t*)out[o]; a.out[o].ld = out_ld[o]; a.out[o].cols = (int)out_cols[o];
+  }
+  hipLaunchKernelGGL(live_mwindows_kernel, dim3(units + (int)nlist, (int)((unit_rows + MW_PIECE - 1) / MW_PIECE)), dim3(256), 0, (hipStream_t)stream, a);
   OP_LAUNCH_CHECK();
   return OP_OK;
 }

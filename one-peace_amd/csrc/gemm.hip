@@ -1042,42 +1042,86 @@ struct GroupArgs {
   int64_t lda, ldb, ldc, ldr;
   const float* alpha;
   int n_seg, N, K, tiles_m, tiles_n, gm;
+  // LIST (op_live_mwindows): the M-tiles are the windows wlist[0 .. *wcount) -- DEVICE memory, written before the launch, never read by
+  // the host -- instead of the 256-row grid; tiles_m / mt_end then only size the launch.  An entry is two words: problem <<
+  // WIN_PROB_SHIFT | first row, and rows << 16 | row stride -- the window's row r is row first + r * stride of the problem (stride 1: a
+  // block of consecutive rows, cut at the problem's end; stride S: one row of each of `rows` <= 256 consecutive S-row samples).
+  const int* wlist; const int* wcount; int max_rstride;  // (a larger stride in an entry: the window stores nothing)
 };
+constexpr int WIN_PROB_SHIFT = 28;  // (a problem has fewer than 2^27 rows: M * lda < 2^30, lda >= 8)
+
+// wave-uniform 32- / 64-bit load through the scalar cache, complete when the statement ends (an asm load: the compiler neither counts
+// nor waits for it; a plain load behind the epilogue's stores would become a vector load with a vmcnt(0) in the middle of the DMA
+// stream).  The wave STALLS here for one scalar-memory latency, and lgkmcnt(0) also waits for its outstanding fragment reads: once per
+// tile, at the top of the tile's main loop, where the next statement is the loop's own lgkmcnt(0) wait -- under a microsecond against
+// the 13 us or more of a K >= 1536 tile.
+__device__ __forceinline__ int uniform_load(const int* q) {
+  int v;
+  // (s_nop 4: the address may come straight from a v_readfirstlane, and an asm statement gets no wait states from the compiler)
+  asm volatile("s_nop 4\n\ts_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(q) : "memory");
+  return v;
+}
+__device__ __forceinline__ unsigned long long uniform_load2(const int* q) {  // q: 8-byte aligned
+  unsigned long long v;
+  asm volatile("s_nop 4\n\ts_load_dwordx2 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(q) : "memory");
+  return v;
+}
 
 template <class T>
 __device__ __forceinline__ T sel3(const T (&a)[3], int i) { return i == 0 ? a[0] : i == 1 ? a[1] : a[2]; }
 
-template <int EPI>
+template <int EPI, bool LIST = false>
 __global__ __launch_bounds__(256) void gemm256p_kernel(const GroupArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int SCHED = 3;
   static_assert(EPI == EPI_BIAS || epi_is_resid(EPI), "gemm256p_kernel: plain / bias and residual epilogues (epilogue_v)");
+  static_assert(!LIST || EPI == EPI_BIAS, "gemm256p_kernel: window lists go with the plain epilogue (input gradients)");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 1, wn = wid & 1;
   const int g = lane >> 4, t = lane & 15;
   constexpr int BN_OUT = 256;
   const int nk = p.K / 64;
-  const int ntiles = p.tiles_m * p.tiles_n;
+  const int tiles_m = LIST ? uniform_load(p.wcount) : p.tiles_m;
+  const int ntiles = tiles_m * p.tiles_n;
   const int stride_b = gridDim.x;
+  if (LIST && (int)blockIdx.x >= ntiles) return;  // (the launch is sized for the dense grid; below, ntiles >= 1)
 
   // ---- tile b -> problem, first row, first column; descriptors of its operand panels (all wave-uniform) ----
-  struct Tile { int prob, m0, n0; const char* a; int na; const char* b0; int nb; };
+  struct Tile { int prob, m0, n0; const char* a; int na; const char* b0; int nb; unsigned ldaB; int rstride, nrows; };
   auto locate = [&](int b) {
     Tile T;
     const bool valid = b < ntiles;
     const int pid = xcd_remap(valid ? b : 0, ntiles);
     const int per_group = p.gm * p.tiles_n;
     const int first_m = (pid / per_group) * p.gm;
-    const int gsz = min(p.tiles_m - first_m, p.gm);
+    const int gsz = min(tiles_m - first_m, p.gm);
     const int in_group = pid % per_group;
     const int pid_m = first_m + in_group % gsz, pid_n = in_group / gsz;
-    T.prob = (pid_m >= p.mt_end[0] ? 1 : 0) + (pid_m >= p.mt_end[1] ? 1 : 0);
-    T.m0 = (pid_m - (T.prob == 0 ? 0 : T.prob == 1 ? p.mt_end[0] : p.mt_end[1])) * BM2;
+    if constexpr (LIST) {  // (pid_m < tiles_m also for a tile past the list, which takes tile 0's entry and fetches nothing)
+      const unsigned long long ee = uniform_load2(p.wlist + 2 * pid_m);  // (both words of the entry in one load)
+      const int e = (int)(unsigned)ee, e1 = (int)(unsigned)(ee >> 32);
+      T.prob = e >> WIN_PROB_SHIFT;
+      T.m0 = e & ((1 << WIN_PROB_SHIFT) - 1);
+      T.rstride = e1 & 0xffff;
+      T.nrows = (e1 >> 16) & 0x1ff;
+    } else {
+      T.rstride = 1; T.nrows = BM2;
+      T.prob = (pid_m >= p.mt_end[0] ? 1 : 0) + (pid_m >= p.mt_end[1] ? 1 : 0);
+      T.m0 = (pid_m - (T.prob == 0 ? 0 : T.prob == 1 ? p.mt_end[0] : p.mt_end[1])) * BM2;
+    }
     T.n0 = pid_n * BN_OUT;
     const int Mp = sel3(p.M, T.prob);
     T.a = (const char*)(sel3(p.A, T.prob) + (int64_t)T.m0 * p.lda);
-    T.na = valid ? (int)((((int64_t)Mp - 1 - T.m0) * p.lda + p.K) * 2) : 0;  // bytes from the tile's first row to the matrix end
+    // bytes from the tile's first row to the matrix end (LIST: an entry that names no row of its problem fetches and stores nothing)
+    T.na = valid && (!LIST || T.m0 < Mp) ? (int)((((int64_t)Mp - 1 - T.m0) * p.lda + p.K) * 2) : 0;
+    if constexpr (LIST) {  // rows the epilogue stores: a strided window must lie inside its problem, or it stores nothing
+      T.nrows = T.rstride == 1 ? min(T.nrows, Mp - T.m0)
+                               : (T.rstride <= p.max_rstride && (int64_t)T.m0 + (int64_t)(T.nrows - 1) * T.rstride < Mp ? T.nrows : 0);
+      T.ldaB = (unsigned)p.lda * (unsigned)T.rstride * 2u;  // (the host checks 256 * stride * lda * 2 < 2^32)
+    } else {
+      T.ldaB = 0;
+    }
     const int seg = T.n0 / p.n_seg, c0 = T.n0 - seg * p.n_seg;
     const bf16_t* w = T.prob == 0 ? (seg == 0 ? p.B[0][0] : seg == 1 ? p.B[0][1] : p.B[0][2])
                     : T.prob == 1 ? (seg == 0 ? p.B[1][0] : seg == 1 ? p.B[1][1] : p.B[1][2])
@@ -1125,8 +1169,12 @@ __global__ __launch_bounds__(256) void gemm256p_kernel(const GroupArgs p) {
   auto rsrc = [&](const char* base, int nrec, int kt) {  // K-tile kt of a panel: base + kt*128 bytes, what is left of it (or nothing)
     return __builtin_amdgcn_make_buffer_rsrc((void*)(base + (int64_t)kt * 128), 0, nrec > 0 ? nrec - kt * 128 : 0, 0x00020000);
   };
-  auto dma_a = [&](const __amdgpu_buffer_rsrc_t& r, char* dst, int j) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(dst + j * 4096), 16, offA, soffA[j], 0, 0);
+  // (LIST: the row stride belongs to the tile -- one multiply-add per eight ops for the per-lane offset, a scalar multiply per op)
+  auto voff_a = [&](const Tile& T) { return LIST ? (unsigned)srow * T.ldaB + (unsigned)(sc * 16) : offA; };
+  auto dma_a = [&](const __amdgpu_buffer_rsrc_t& r, char* dst, int j, unsigned voff, const Tile& T) {
+    unsigned soff = soffA[j];
+    if constexpr (LIST) soff = (unsigned)(j * 32) * T.ldaB;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)(dst + j * 4096), 16, voff, soff, 0, 0);
   };
   auto dma_b = [&](const __amdgpu_buffer_rsrc_t& r0, char* dst, int j) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r0, (__attribute__((address_space(3))) void*)(dst + j * 4096), 16, offB, soffB[j], 0, 0);
@@ -1135,9 +1183,10 @@ __global__ __launch_bounds__(256) void gemm256p_kernel(const GroupArgs p) {
   auto issue_tile = [&](bool is_b, const Tile& T, int kt) {
     char* dst = smem + qslot_issue * SLOT3_BYTES + wid * 1024;
     const __amdgpu_buffer_rsrc_t ra = rsrc(T.a, T.na, kt), rb0 = rsrc(T.b0, T.nb, kt);
+    const unsigned va = voff_a(T);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      if (is_b) dma_b(rb0, dst, j); else dma_a(ra, dst, j);
+      if (is_b) dma_b(rb0, dst, j); else dma_a(ra, dst, j, va, T);
     }
     next_slot();
   };
@@ -1146,6 +1195,7 @@ __global__ __launch_bounds__(256) void gemm256p_kernel(const GroupArgs p) {
     constexpr bool IS_B = decltype(b_tag)::value;
     char* dst = smem + qslot_issue * SLOT3_BYTES + wid * 1024;
     const __amdgpu_buffer_rsrc_t r0 = IS_B ? rsrc(T.b0, T.nb, kt) : rsrc(T.a, T.na, kt);
+    const unsigned va = voff_a(T);
     auto rd = [&](int r) {
       if (r < 8) nxt_w[r] = *reinterpret_cast<const bf16x8*>(sb + w_off(r) + fsw[h]);
       else nxt_x[r - 8] = *reinterpret_cast<const bf16x8*>(sa + rowX + (r - 8) * 2048 + fsw[h]);
@@ -1159,7 +1209,7 @@ __global__ __launch_bounds__(256) void gemm256p_kernel(const GroupArgs p) {
         __builtin_amdgcn_sched_barrier(0);
         if (rd0 >= 0) rd(rd0);
         if (rd1 >= 0) rd(rd1);
-        if (d >= 0) { if (IS_B) dma_b(r0, dst, d); else dma_a(r0, dst, d); }
+        if (d >= 0) { if (IS_B) dma_b(r0, dst, d); else dma_a(r0, dst, d, va, T); }
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -1210,14 +1260,17 @@ __global__ __launch_bounds__(256) void gemm256p_kernel(const GroupArgs p) {
     {  // epilogue of the finished tile; its stores drain while the next tile's main loop runs
       GemmArgs q;
       q.M = sel3(p.M, cur.prob); q.N = p.N; q.K = p.K; q.n_seg = p.n_seg; q.ldc = p.ldc; q.ldr = p.ldr; q.m_off = 0;
-      q.C = sel3(p.C, cur.prob); q.H0 = sel3(p.H0, cur.prob); q.H1 = sel3(p.H1, cur.prob);
+      q.C = sel3(p.C, cur.prob);
+      if constexpr (LIST) {  // the window as a matrix of its own: `nrows` rows from the window's first row on, `rstride` rows apart
+        q.C = (bf16_t*)q.C + (int64_t)cur.m0 * p.ldc; q.ldc = p.ldc * cur.rstride; q.M = cur.nrows;
+      } q.H0 = sel3(p.H0, cur.prob); q.H1 = sel3(p.H1, cur.prob);
       q.resid = sel3(p.resid, cur.prob); q.gamma = sel3(p.gamma, cur.prob); q.rowscale = sel3(p.rowscale, cur.prob);
       q.rows_per_sample = sel3(p.rows_per_sample, cur.prob); q.alpha = p.alpha; q.rows = sel3(p.rows, cur.prob);
       q.bias[0] = q.bias[1] = q.bias[2] = nullptr;  // (unused: the tile's bias vector travels as an argument, see gemm_epilogue)
       // the tile lies in ONE weight segment (n_seg is a multiple of the tile width, checked at launch): kernel-argument table look-up
       const int segt = cur.n0 / p.n_seg;
       const bf16_t* bt = p.bias[cur.prob][segt];
-      epilogue_v<EPI>(q, acc, cur.m0 + wm * 128, cur.n0 + wn * 128, g, t, bt, true);
+      epilogue_v<EPI>(q, acc, (LIST ? 0 : cur.m0) + wm * 128, cur.n0 + wn * 128, g, t, bt, true);
     }
     zero_acc();
     cur = nxt;
@@ -2119,17 +2172,18 @@ static int num_cus() {
   return n > 0 ? n : 8;
 }
 
-template <int EPI>
+template <int EPI, bool LIST = false>
 int launch256p(const GroupArgs& ga, hipStream_t s, bool persistent = true) {
   const size_t sh = (size_t)SLOTS3 * SLOT3_BYTES;
-  OP_ENSURE_LDS((gemm256p_kernel<EPI>), sh, "gemm256p");
-  const int ntiles = ga.tiles_m * ga.tiles_n;
-  hipLaunchKernelGGL((gemm256p_kernel<EPI>), dim3((!persistent || ntiles < num_cus()) ? ntiles : num_cus()), dim3(256), sh, s, ga);
+  OP_ENSURE_LDS((gemm256p_kernel<EPI, LIST>), sh, "gemm256p");
+  const int ntiles = ga.tiles_m * ga.tiles_n;  // (LIST: the most the list can hold; workgroups past the device's count leave at once)
+  hipLaunchKernelGGL((gemm256p_kernel<EPI, LIST>), dim3((!persistent || ntiles < num_cus()) ? ntiles : num_cus()), dim3(256), sh, s, ga);
   OP_LAUNCH_CHECK();
   return OP_OK;
 }
 
 static int launch256p_any(const GroupArgs& ga, int epi, hipStream_t s, bool persistent) {
+  if (ga.wlist) return launch256p<EPI_BIAS, true>(ga, s, persistent);  // (the entry has checked: plain epilogue)
   return op_with_int<EPI_BIAS, EPI_RESID, EPI_RESID_ROWS>(epi, [&](auto e) { return launch256p<decltype(e)::value>(ga, s, persistent); });
 }
 
@@ -2592,12 +2646,17 @@ int op_gemm_nt(const void* A, int64_t lda, const void* B0, const void* B1, const
 // gamma, rowscale, bias entries may be null, a whole array pointer may be null.  Epilogues 0 (bias), 3 (residual); 2 (GeGLU) returns
 // OP_ENOTSUP since round 5 (h1 and the second weight of a problem are unused).  Requirements: N % 256 == 0, K % 64 == 0, K >= 128, lda / ldb / ldc % 8 == 0, every operand below 2 GiB.
 // Returns OP_ENOTSUP when the shape does not qualify (the caller then launches the problems one by one).
-int op_gemm_nt_grouped(int64_t nprob, const void* const* A, const int64_t* M, int64_t lda, const void* const* B, int64_t ldb,
-                       const void* const* bias, void* const* C, int64_t ldc, void* const* h0, void* const* h1,
-                       const void* const* resid, int64_t ldr, const void* const* gamma, const float* const* rowscale,
-                       const int64_t* rows_per_sample, int64_t N, int64_t K, int epilogue, int64_t tune, const int* const* resid_rows,
-                       int64_t resid_rows_total, void* stream) {
+static int gemm_nt_grouped_impl(int64_t nprob, const void* const* A, const int64_t* M, int64_t lda, const void* const* B, int64_t ldb,
+                                const void* const* bias, void* const* C, int64_t ldc, void* const* h0, void* const* h1,
+                                const void* const* resid, int64_t ldr, const void* const* gamma, const float* const* rowscale,
+                                const int64_t* rows_per_sample, int64_t N, int64_t K, int epilogue, int64_t tune, const int* const* resid_rows,
+                                int64_t resid_rows_total, const int32_t* windows, const int32_t* n_windows, int64_t max_windows,
+                                int64_t max_row_stride, void* stream) {
   const GemmTune T = decode_tune(tune);
+  if (windows)
+    OP_CHECK_ARG(n_windows && ((uintptr_t)windows & 7) == 0 && max_windows >= 1 && max_windows < ((int64_t)1 << 24) && epilogue == EPI_BIAS && !resid_rows &&
+                 max_row_stride >= 1 && max_row_stride < 65536 && max_row_stride * lda < ((int64_t)1 << 23) && max_row_stride * ldc < ((int64_t)1 << 23),
+                 "gemm_nt_grouped_windows: 8-byte aligned list, count, 1 <= max_windows < 2^24, plain epilogue, no row table, max_row_stride * lda (ldc) < 2^23");
   if (resid_rows) {  // (ABI 9) see op_gemm_nt: all problems or none, one row count for all the full matrices
     OP_CHECK_ARG(epilogue == EPI_RESID && resid_rows_total > 0 && ldr % 8 == 0 &&
                  (resid_rows_total * (ldc > ldr ? ldc : ldr) + N) * 2 < (int64_t)0xfff00000ll,
@@ -2645,7 +2704,8 @@ int op_gemm_nt_grouped(int64_t nprob, const void* const* A, const int64_t* M, in
     }
     ga.mt_end[i] = tiles;
   }
-  ga.tiles_m = tiles;
+  ga.tiles_m = windows ? (int)max_windows : tiles;
+  ga.wlist = windows; ga.wcount = n_windows; ga.max_rstride = (int)max_row_stride;
   ga.tiles_n = (int)(N / bn);
   ga.lda = lda; ga.ldb = ldb; ga.ldc = ldc; ga.ldr = ldr; ga.alpha = nullptr;
   ga.n_seg = (int)N; ga.N = (int)N; ga.K = (int)K;
@@ -2658,6 +2718,33 @@ int op_gemm_nt_grouped(int64_t nprob, const void* const* A, const int64_t* M, in
   const int rc = launch256p_any(ga, resid_rows ? (int)EPI_RESID_ROWS : epilogue, (hipStream_t)stream, T.sched != 7);
   op_prof_end(slot, stream);
   return rc;
+}
+
+int op_gemm_nt_grouped(int64_t nprob, const void* const* A, const int64_t* M, int64_t lda, const void* const* B, int64_t ldb,
+                       const void* const* bias, void* const* C, int64_t ldc, void* const* h0, void* const* h1,
+                       const void* const* resid, int64_t ldr, const void* const* gamma, const float* const* rowscale,
+                       const int64_t* rows_per_sample, int64_t N, int64_t K, int epilogue, int64_t tune, const int* const* resid_rows,
+                       int64_t resid_rows_total, void* stream) {
+  return gemm_nt_grouped_impl(nprob, A, M, lda, B, ldb, bias, C, ldc, h0, h1, resid, ldr, gamma, rowscale, rows_per_sample, N, K, epilogue,
+                              tune, resid_rows, resid_rows_total, nullptr, nullptr, 0, 1, stream);
+}
+
+// (additive: op_abi_version() stays 10) op_gemm_nt_grouped's plain form over a WINDOW LIST: the launch computes the windows
+// windows[0 .. *n_windows) name (an entry is two words: problem << 28 | first row inside the problem, and rows << 16 | row stride; with
+// stride 1 a block of up to 256 consecutive rows from any row on -- blocks may overlap and may run past a problem's end, where rows
+// are fetched as zeros and not stored --, with stride S <= max_row_stride one row of each of `rows` consecutive S-row samples) and
+// writes NO other row of C -- op_live_mwindows builds the list from the stochastic-depth multipliers and zero-fills the rest.
+// windows / n_windows: DEVICE int32 [2 * max_windows] / [1], written
+// before the launch on the same stream, never read by the host; max_windows sizes the grid.  Each listed block is the same bits
+// as in the dense launch (same operands, same K order).  The profiling slot counts the nominal 2 M N K.
+int op_gemm_nt_grouped_windows(int64_t nprob, const void* const* A, const int64_t* M, int64_t lda, const void* const* B, int64_t ldb,
+                               void* const* C, int64_t ldc, int64_t N, int64_t K, const int32_t* windows, const int32_t* n_windows,
+                               int64_t max_windows, int64_t max_row_stride, int64_t tune, void* stream) {
+  OP_CHECK_ARG(windows && n_windows && B && nprob >= 1 && nprob <= 3, "gemm_nt_grouped_windows: null list / weights, 1..3 problems");
+  const void* B2[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // (B: ONE weight per problem)
+  for (int i = 0; i < (int)nprob; ++i) B2[i * 2] = B[i];
+  return gemm_nt_grouped_impl(nprob, A, M, lda, B2, ldb, nullptr, C, ldc, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, N, K,
+                              EPI_BIAS, tune, nullptr, 0, windows, n_windows, max_windows, max_row_stride, stream);
 }
 
 // C[M,N] (bf16, ldc) = A^T B with A [K, M] (lda) and B [K, N] (ldb) both row-major bf16: the weight-gradient GEMM

@@ -44,6 +44,8 @@ SIGNATURES = {
     "op_gemm_tn_grouped": (c_int, [I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P]),
     "op_gemm_tn_grouped_lists": (c_int, [I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, P]),
     "op_live_ktiles": (c_int, [I64, P, P, P, P, I64, P, P, P, P, P]),
+    "op_live_mwindows": (c_int, [I64, P, P, P, P, P, P, P, P, P, P, I64, P, P, P, I64, P, P, P, P, P]),
+    "op_gemm_nt_grouped_windows": (c_int, [I64, P, P, I64, P, I64, P, I64, I64, I64, P, P, I64, I64, I64, P]),
     "op_gemm_nt_batched": (c_int, [P, I64, I64, P, I64, I64, P, I64, P, I64, I64, I64, I64, I64, I64, P]),
     "op_audio_conv1_ln_gelu_fwd": (c_int, [P, I64, P, P, P, P, P, P, P, I64, I64, c_float, P]),
     "op_audio_conv1_ln_gelu_bwd_workspace_bytes": (I64, [I64]),
@@ -359,6 +361,18 @@ SPLITK_WS_BYTES = 768 << 20
 GEMM_ALGO_BYTES = [0, 0]  # [bytes, launches]: operands read once + outputs written once (bench.py's roofline.traffic yardstick)
 
 
+def splitk_scratch(M, N, K, epilogue, device):
+    """The fp32 scratch gemm_nt hands to op_gemm_nt for an [M, K] x [N, K]^T launch (the planner may then split K), or None: bias-free
+    plain launches with few tiles and a long K (weight gradients, dgrads), and the small latency-bound launches (a few M-tiles: the
+    leftover rows of a tail-rows split, batch-1 feature extraction) whose bias / residual epilogue the fold kernel applies.  The library
+    decides; handing the scratch over costs nothing.  (ops._dense_dgrad_sums_k_in_one_piece asks the same question through this.)"""
+    if epilogue in (EPI_BIAS, EPI_RESID) and (K >= 2048 or M <= 1024):
+        # at most 8 fp32 slabs of the output (the planner's limit); small launches (feature extraction under hipGraph
+        # capture, where every capture stream gets its own scratch) then pin megabytes, not the training-size buffer
+        return workspace(min(SPLITK_WS_BYTES, 32 * M * N), device, "gemm_splitk")
+    return None
+
+
 def gemm_nt(A, Bs, biases=None, out=None, epilogue=EPI_BIAS, n_seg=0, h0=None, h1=None, resid=None, gamma=None,
             rowscale=None, rows_per_sample=0, alpha=None, N=None, ldc=None, splitk=True, resid_rows=None):
     """C[M,N] = A[M,K] @ cat(Bs)[N,K]^T with the fused epilogue.  Bs: list of 1-3 [n_seg,K] weights (GeGLU: [W0, W1]).
@@ -379,15 +393,8 @@ def gemm_nt(A, Bs, biases=None, out=None, epilogue=EPI_BIAS, n_seg=0, h0=None, h
     if out is None:
         out = torch.empty(M, Nn, dtype=torch.float32 if epilogue == EPI_F32 else torch.bfloat16, device=A.device)
     ldc_ = ldc if ldc is not None else out.stride(0)
-    ws, ws_bytes = None, 0
-    # fp32 scratch for split-K: bias-free plain launches with few tiles and a long K (weight gradients, dgrads), and the
-    # small latency-bound launches (a few M-tiles: the leftover rows of a tail-rows split, batch-1 feature extraction)
-    # whose bias / residual epilogue the fold kernel applies.  The library decides; handing the scratch over costs nothing.
-    if splitk and epilogue in (EPI_BIAS, EPI_RESID) and (K >= 2048 or M <= 1024):
-        # at most 8 fp32 slabs of the output (the planner's limit); small launches (feature extraction under hipGraph
-        # capture, where every capture stream gets its own scratch) then pin megabytes, not the training-size buffer
-        ws = workspace(min(SPLITK_WS_BYTES, 32 * M * Nn), A.device, "gemm_splitk")
-        ws_bytes = ws.numel()
+    ws = splitk_scratch(M, Nn, K, epilogue, A.device) if splitk else None
+    ws_bytes = ws.numel() if ws is not None else 0
     outs = 1 + (2 if h1 is not None else (1 if h0 is not None else 0))
     GEMM_ALGO_BYTES[0] += 2 * (M * K + Nn * K * (2 if epilogue == EPI_GEGLU else 1) + (M * Nn if resid is not None else 0)) \
         + out.element_size() * M * Nn * outs
@@ -575,6 +582,81 @@ def live_ktiles(segs, probs, device):
                                 i64(ns, [q[3] for q in segs]), n, i64(n, [q[0] for q in probs]), i64(n, [q[1] for q in probs]),
                                 _ptr_array([q[0] for q in lists], n), _ptr_array([q[1] for q in lists], n), stream()), "op_live_ktiles")
     return lists
+
+
+def mwindow_rule(S):
+    """How a segment of S-row samples is cut into 256-row windows for the input-gradient GEMMs: (wps, odd).  wps > 0: every kept sample
+    gets wps windows from its first row on -- chosen when they carry at most 5 % surplus rows; odd: S % 256 == 1, the windows leave
+    out each sample's last row, and those rows of ALL samples form strided windows (256 samples each).  wps == 0: the aligned 256-row
+    tiles of the segment."""
+    odd = S % 256 == 1 and S > 1
+    Sp = S - 1 if odd else S
+    wps = -(-Sp // 256)
+    if wps * 256 * 100 <= 105 * Sp:
+        return wps, odd
+    return 0, False
+
+
+def live_mwindows(segs, lists, outs):
+    """Window lists (op_live_mwindows) for input-gradient GEMMs over one row matrix whose rows of dropped samples are zero, and +0 in
+    the rows of `outs` the listed launches will not write.  segs: [(ps fp32 | None, row0, S, B[, ps stride = 1])], sample b has the multiplier ps[b * stride]; lists: per list the members
+    [(segment index, problem index, row at which the problem's operand starts)], a segment in at most two lists; outs: bf16 matrices
+    parallel to the row matrix.  Returns per list (windows int32 [2 * max] -- two words per entry --, count int32 [1]): views of ONE buffer, never read by the host."""
+    ns, nl, no = len(segs), len(lists), len(outs)
+    dev = outs[0].device if outs else next(q[0] for q in segs if q[0] is not None).device
+    segs = [tuple(q) + (1,) * (5 - len(q)) for q in segs]
+    wps = [mwindow_rule(q[2])[0] for q in segs]
+    odd = [int(mwindow_rule(q[2])[1]) for q in segs]
+    units = [(q[3] if w else -(-q[2] * q[3] // 256)) * max(w, 1) + (-(-q[3] // 256) if o else 0) for w, o, q in zip(wps, odd, segs)]
+    sizes = [sum(units[i] for i, _, _ in members) for members in lists]
+    buf = torch.empty(2 * sum(sizes) + nl + (nl & 1), dtype=torch.int32, device=dev)
+    res, off = [], nl + (nl & 1)  # (the two-word entries stay 8-byte aligned: the GEMM reads one with a single 64-bit load)
+    for l, k in enumerate(sizes):
+        res.append((buf[off:off + 2 * k], buf[l:l + 1]))
+        off += 2 * k
+    ref = [[-1, 0, 0, -1, 0, 0] for _ in segs]
+    for l, members in enumerate(lists):
+        for i, prob, base in members:
+            k = 0 if ref[i][0] < 0 else 3
+            assert ref[i][k] < 0, "a segment feeds at most two lists"
+            ref[i][k:k + 3] = [l, prob, base]
+    i64 = lambda vals: (c_int64 * len(vals))(*[int(v) for v in vals])  # noqa: E731
+    for ps, _, _, B, st in segs:
+        assert ps is None or (ps.dtype == torch.float32 and ps.is_contiguous() and ps.numel() > (B - 1) * st and ps.device == buf.device)
+    for o in outs:
+        assert o.dtype == torch.bfloat16 and o.dim() == 2 and o.stride(1) == 1 and o.device == buf.device
+    _check(lib().op_live_mwindows(ns, _ptr_array([q[0] for q in segs], ns), i64([q[4] for q in segs]), i64([q[1] for q in segs]),
+                                  i64([q[2] for q in segs]), i64([q[3] for q in segs]), i64(wps), i64(odd), i64([v for r in ref for v in (r[0], r[3])]),
+                                  i64([v for r in ref for v in (r[1], r[4])]), i64([v for r in ref for v in (r[2], r[5])]), nl,
+                                  _ptr_array([q[0] for q in res], nl), _ptr_array([q[1] for q in res], nl), i64(sizes), no,
+                                  _ptr_array(outs, max(no, 1)), i64([o.stride(0) for o in outs] or [0]), i64([o.shape[1] for o in outs] or [0]),
+                                  i64([o.shape[0] for o in outs] or [0]), stream()), "op_live_mwindows")
+    return res
+
+
+def gemm_nt_windows(As, Ws, outs, windows, max_row_stride=1, tune=None):
+    """The rows of out_p = A_p @ W_p^T that the entries of `windows` (live_mwindows' (list, count)) name, nothing else: one launch of the
+    persistent kernel for up to three problems with a common N, K and row strides.  max_row_stride: the largest sample length with
+    strided windows in the list (mwindow_rule's odd).  Returns False (nothing launched) when the shape does not qualify."""
+    n = len(As)
+    K, N = As[0].shape[1], Ws[0].shape[0]
+    lda, ldb, ldc = As[0].stride(0), Ws[0].stride(0), outs[0].stride(0)
+    assert all(a.stride(0) == lda and a.shape[1] == K and a.stride(1) == 1 for a in As) and all(o.stride(0) == ldc and o.shape[1] == N for o in outs)
+    assert all(w.stride(0) == ldb and w.shape == (N, K) for w in Ws) and all(o.shape[0] == a.shape[0] for a, o in zip(As, outs))
+    lst, cnt = windows
+    assert lst.dtype == torch.int32 and cnt.dtype == torch.int32 and lst.is_contiguous() and lst.numel() >= 2 and lst.data_ptr() % 8 == 0
+    if max_row_stride * max(lda, ldc) >= 1 << 23:
+        return False
+    rc = lib().op_gemm_nt_grouped_windows(n, _ptr_array(As, n), (c_int64 * n)(*[a.shape[0] for a in As]), lda, _ptr_array(Ws, n), ldb,
+                                          _ptr_array(outs, n), ldc, N, K, ptr(lst), ptr(cnt), lst.numel() // 2, max_row_stride,
+                                          TUNE.gemm() if tune is None else int(tune), stream())
+    if rc == -95:
+        return False
+    _check(rc, "op_gemm_nt_grouped_windows")
+    for a in As:  # (the dense launch's bytes and, in the profiling slot, its 2 M N K: both overstate a listed launch by the skipped share)
+        GEMM_ALGO_BYTES[0] += 2 * (a.shape[0] * K + N * K) + 2 * a.shape[0] * N
+    GEMM_ALGO_BYTES[1] += 1
+    return True
 
 
 def gemm_tn_grouped(problems, tune=0, ktiles=None):

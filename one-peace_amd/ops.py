@@ -305,6 +305,49 @@ def _live_ktiles(segs, probs, device):
     return hip.live_ktiles(segs, probs, device)
 
 
+# The INPUT gradients of such a branch (dy W^T: the token rows are the M dimension) multiply those zero rows into zero rows.  "1": they
+# run only the 256-row windows hip.live_mwindows lists (windows that start at a kept sample's first row where a sample nearly fills
+# them, aligned tiles with a kept row elsewhere -- hip.mwindow_rule), one tiny launch per branch builds the lists and writes +0 into the
+# rows no window covers; the last rows of S % 256 == 1 samples form strided windows of the same launch.  The same bits: a
+# listed row is the dense launch's row (same operands, same K order), a dense row of zeros is +0; a non-finite gradient in a dropped
+# sample's row gives 0 where the dense launch gives NaN.  "0": the dense launches (A/B, tests).
+SKIP_ZERO_DGRAD = os.environ.get("ONEPEACE_SKIP_ZERO_DGRAD", "1") != "0"
+_dense_dgrad_plans = {}
+
+
+def _dense_dgrad_sums_k_in_one_piece(M, N, K, device):
+    """Does hip.gemm_nt run this input gradient without a K-split (main launch and tail rows)?  Only then a listed window, which never
+    splits, has the dense launch's bits.  (Training shapes: yes -- the planner splits K for launches of a few M-tiles.)  The scratch is
+    the one that launch would get, at its size of this moment."""
+    scratch = hip.splitk_scratch(M, N, K, hip.EPI_BIAS, device)
+    ws = scratch.numel() if scratch is not None else 0
+    key = (M, N, K, ws, hip.TUNE.gemm())
+    if key not in _dense_dgrad_plans:
+        _, splits, _, tail = hip.gemm_plan(M, N, K, hip.EPI_BIAS, False, ws)
+        _dense_dgrad_plans[key] = splits == 1 and (tail == 0 or hip.gemm_plan(tail, N, K, hip.EPI_BIAS, False, ws)[1] == 1)
+    return _dense_dgrad_plans[key]
+
+
+def _dgrad_windows(segs, lists, outs, dense):
+    """hip.live_mwindows' lists for the input gradients of a branch, or None when they do not apply: switched off, no multipliers, a
+    shape the persistent kernel does not take, or a dense launch ([(M, N, K)], the per-problem launches the lists replace) that would
+    split K.  segs: [(ps, row0, S, B, ps stride)]."""
+    if not SKIP_ZERO_DGRAD or all(q[0] is None for q in segs) or len(segs) > 4 or len(lists) > 4 or len(outs) > 4:
+        return None
+    if any(N % 256 != 0 or K % 64 != 0 or K < 128 or not _dense_dgrad_sums_k_in_one_piece(M, N, K, outs[0].device) for M, N, K in dense):
+        return None
+    if any(ps is not None and (ps.dtype != torch.float32 or not ps.is_contiguous() or ps.numel() <= (B - 1) * st) for ps, _, _, B, st in segs):
+        return None
+    if any(o.dtype != torch.bfloat16 or o.stride(0) % 8 != 0 or o.shape[1] % 8 != 0 for o in outs):
+        return None
+    return hip.live_mwindows(segs, lists, outs)
+
+
+def _dgrad_listed(As, Ws, outs, windows, segs):
+    """outs[p] = As[p] Ws[p]^T over a window list built for `segs`.  False: nothing launched (the caller runs the dense launch)."""
+    return hip.gemm_nt_windows(As, Ws, outs, windows, max([sg.S for sg in segs if hip.mwindow_rule(sg.S)[1]] or [1]))
+
+
 class _WgradQueue:
     """Weight-gradient GEMMs that accumulate into flat gradient views, collected while a layer's backward runs (FFN branch
     first, then the attention branch, which flushes): launched alone each of them has 36 ... 288 output tiles for 256 CUs and
@@ -1215,7 +1258,8 @@ class AttnBranchFn(torch.autograd.Function):
         # out-proj and q|k|v weight gradients: both run over ALL rows, one list serves both (rows of dropped samples are zero in dy1, and
         # so in everything the branch derives from it)
         kt1 = None
-        if rowscale is not None and kept is None and N % rps == 0 and not any(sg.pad for sg in segs) and sum(sg.rows for sg in segs) == N:
+        whole = rowscale is not None and kept is None and N % rps == 0 and not any(sg.pad for sg in segs) and sum(sg.rows for sg in segs) == N
+        if whole:
             kt1 = _live_ktiles([(rowscale, 0, rps, N // rps)], [(0, N)], dx_mid.device)[0]
         if ctx.dg_fused:  # dy1 = rowscale * dx_mid, WITHOUT gamma_1 (weight gradient: rscale; input gradient: scaled weight copy)
             g0 = torch.empty(H, dtype=torch.float32, device=dx_mid.device)
@@ -1232,7 +1276,19 @@ class AttnBranchFn(torch.autograd.Function):
         upstream = ("ln1_w", "ln1_b", "wq", "bq", "wk", "wv", "bv", "aln_w", "aln_b")
         dx = None
         if need_x or any(want_dbias) or any(needs[n] for n in upstream):
-            daln = hip.gemm_nt(dy1, [wo_t if wo_t is not None else _transposed(P["wo"])])
+            # the two input gradients over all rows (out-proj, q|k|v) share ONE window list; their outputs exist before it is built,
+            # because the launch that builds it also writes the zero rows
+            need_dxln1 = need_x or needs["ln1_w"] or needs["ln1_b"]
+            win1, daln, dxln1 = None, None, None
+            if whole and all(sg.S % rps == 0 and sg.row0 % rps == 0 for sg in segs):
+                daln = torch.empty(N, H, dtype=dy1.dtype, device=dy1.device)
+                dxln1 = torch.empty_like(daln) if need_dxln1 else None
+                win1 = _dgrad_windows([(rowscale[sg.row0 // rps:], sg.row0, sg.S, sg.B, sg.S // rps) for sg in segs],
+                                      [[(i, 0, 0) for i in range(nseg)]], [daln] + ([dxln1] if need_dxln1 else []),
+                                      [(N, H, H)] + ([(N, H, 3 * H)] if need_dxln1 else []))
+            wo_in = wo_t if wo_t is not None else _transposed(P["wo"])
+            if win1 is None or not _dgrad_listed([dy1], [wo_in], [daln], win1[0], segs):
+                daln = hip.gemm_nt(dy1, [wo_in])
             if P["aln_w"] is not None:
                 want = needs["aln_w"] or needs["aln_b"]
                 (tw, tb), acc = _targets(direct, "aln_w", "aln_b") if want else ((None, None), False)
@@ -1283,8 +1339,10 @@ class AttnBranchFn(torch.autograd.Function):
             else:
                 dW = wgrad(dqkv, A["xln1"])  # [3H, H]
                 G["wq"], G["wk"], G["wv"] = dW[:H], dW[H:2 * H], dW[2 * H:]
-            if need_x or needs["ln1_w"] or needs["ln1_b"]:
-                dxln1 = hip.gemm_nt(dqkv, [_transposed(tuple(P[n] for n in cols))])
+            if need_dxln1:
+                wqkv_t = _transposed(tuple(P[n] for n in cols))
+                if win1 is None or not _dgrad_listed([dqkv], [wqkv_t], [dxln1], win1[0], segs):
+                    dxln1 = hip.gemm_nt(dqkv, [wqkv_t])
                 want = needs["ln1_w"] or needs["ln1_b"]
                 (tw, tb), acc = _targets(direct, "ln1_w", "ln1_b") if want else ((None, None), False)
                 # (mapped: the kept samples' rows of a NEW full matrix -- the incoming gradient may be the caller's tensor --, the dropped
@@ -1509,6 +1567,16 @@ class FfnBranchMultiFn(torch.autograd.Function):
         kts = [None] * nseg
         if kept is None and not any(sg.pad for sg in segs):
             kts = _live_ktiles([(pss[i], sg.row0, sg.S, sg.B) for i, sg in enumerate(segs)], [(sg.row0, sg.rows) for sg in segs], dev)
+        # input gradients: list i for segment i's down-projection launch, list nseg for the grouped wi_0 | wi_1 launch of all segments
+        # (entries carry the problem index); the fp8 route stays dense
+        need_dxln2 = upstream and (need_x or needs["ln2_w"] or needs["ln2_b"])
+        wins, dxln2 = None, None
+        if upstream and kept is None and not any(sg.pad for sg in segs) and not fp8b:
+            dxln2 = torch.empty(N, H, dtype=dt, device=dev) if need_dxln2 else None
+            wins = _dgrad_windows([(pss[i], sg.row0, sg.S, sg.B, 1) for i, sg in enumerate(segs)],
+                                  [[(i, 0, sg.row0)] for i, sg in enumerate(segs)] + ([[(i, i, sg.row0) for i, sg in enumerate(segs)]] if need_dxln2 else []),
+                                  [dgln] + ([dxln2] if need_dxln2 else []),
+                                  [(sg.rows, Fd, H) for sg in segs] + ([(sg.rows, H, 2 * Fd) for sg in segs] if need_dxln2 and nseg == 1 else []))
         for i, sg in enumerate(segs):
             r = slice(sg.row0, sg.end)
             k = lambda n: "%s@%d" % (n, i)  # noqa: E731
@@ -1530,7 +1598,7 @@ class FfnBranchMultiFn(torch.autograd.Function):
             w2t = _transposed(P[k("w2")], scale=P["g2"] if fused else None)
             if fp8b:  # (opt-in, round 6) d LN_F(g) = dy W2 on e4m3 operands: the gradient rows and the transposed weight copy row-quantised
                 hip.gemm_nt_fp8(*hip.quant_fp8_rows(dy2), *[[x] for x in _fp8_derived(w2t)], out=dgln[r])
-            else:
+            elif wins is None or not _dgrad_listed([dy2], [w2t], [dgln[r]], wins[i], [sg]):
                 hip.gemm_nt(dy2, [w2t], out=dgln[r])
             pair = (k("w0"), k("w1"))
             order = _adjacent_grads(direct, pair) if needs[pair[0]] and needs[pair[1]] and Fd % 8 == 0 else None
@@ -1560,13 +1628,16 @@ class FfnBranchMultiFn(torch.autograd.Function):
             else:
                 _direct_grad_done(direct["g2"])
         dx = None
-        if upstream and (need_x or needs["ln2_w"] or needs["ln2_b"]):
-            dxln2 = torch.empty(N, H, dtype=dt, device=dev)
+        if need_dxln2:
+            if dxln2 is None:
+                dxln2 = torch.empty(N, H, dtype=dt, device=dev)
             rs = [slice(sg.row0, sg.end) for sg in segs]
             wts = [_transposed(tuple(P[n] for n in cols)) for cols in colsets]
             if fp8b:  # one fp8 launch per modality (the grouped persistent launch is bf16 only)
                 for r, wt in zip(rs, wts):
                     hip.gemm_nt_fp8(*hip.quant_fp8_rows(dh[r]), *[[x] for x in _fp8_derived(wt)], out=dxln2[r])
+            elif wins is not None and _dgrad_listed([dh[r] for r in rs], wts, [dxln2[r] for r in rs], wins[nseg], segs):
+                pass
             elif nseg == 1 or hip.gemm_nt_grouped([dh[r] for r in rs], wts, outs=[dxln2[r] for r in rs]) is None:
                 for r, wt in zip(rs, wts):
                     hip.gemm_nt(dh[r], [wt], out=dxln2[r])
