@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* ---- library ------------------------------------------------------------------------------------------------ */
-int op_abi_version(void); /* 2: per-call `tune` words replaced the process-wide knob setters; 3: op_gemm_nt_grouped, op_ln_geglu_fwd, ldd / ldh of op_ln_geglu_bwd, `out` of op_attn_bwd; 4: op_gemm_tn_grouped; 5: op_probe_mfma_rate, op_rows_gather / op_rows_merge, 16-byte rule of op_gemm_tn_grouped's C; 6: the op_probe_* entry points left for libonepeace_probe.so (include/onepeace_probe.h), op_gemm_nt_grouped answers OP_ENOTSUP for the GeGLU epilogue, op_gemm_tn_grouped_plan takes the workgroup count and tune word; 7: W / ldw / rowdot of op_gemm_tn_grouped, g0 of op_resid_bwd, op_gamma_grad_finish, op_gemm_nt_batched, op_audio_conv1_ln_gelu_fwd / _bwd; 8: the layer-scale gradient without a division -- rscale of op_gemm_tn_grouped, op_transpose_scaled + the scale member of the op_transpose_batched descriptor, op_resid_bwd leaves gamma out of dbranch when g0 is asked for, op_gamma_grad_finish lost its gamma argument; rowdot is a [N / 128][M] matrix of partial sums written once each (no atomics); 9: row tables -- a residual branch that runs on the samples stochastic depth keeps reads and writes the FULL activation matrix through op_rows_map's table instead of through packed copies: x_rows of op_layernorm_fwd / op_layernorm_bwd, dout_rows of op_resid_bwd, resid_rows / resid_rows_total of op_gemm_nt and op_gemm_nt_grouped, op_rows_merge without `upd` copies the dropped samples' rows only; op_prof_reserve; 10: run-to-run identical gradients -- op_relpos_bias_bwd sums the table gradient in a fixed order from pair lists instead of scattering with atomics, op_relpos_bias_bwd_ids became op_relpos_bias_fold_ids, the separate dBias kernel of op_attn_bwd adds into one slab per batch chunk; (still 10, additive) op_live_ktiles + op_gemm_tn_grouped_lists: the weight gradients skip the K-tiles of samples stochastic depth dropped; (still 10, additive) op_live_mwindows + op_gemm_nt_grouped_windows: the input gradients skip their row blocks */
+int op_abi_version(void); /* 2: per-call `tune` words replaced the process-wide knob setters; 3: op_gemm_nt_grouped, op_ln_geglu_fwd, ldd / ldh of op_ln_geglu_bwd, `out` of op_attn_bwd; 4: op_gemm_tn_grouped; 5: op_probe_mfma_rate, op_rows_gather / op_rows_merge, 16-byte rule of op_gemm_tn_grouped's C; 6: the op_probe_* entry points left for libonepeace_probe.so (include/onepeace_probe.h), op_gemm_nt_grouped answers OP_ENOTSUP for the GeGLU epilogue, op_gemm_tn_grouped_plan takes the workgroup count and tune word; 7: W / ldw / rowdot of op_gemm_tn_grouped, g0 of op_resid_bwd, op_gamma_grad_finish, op_gemm_nt_batched, op_audio_conv1_ln_gelu_fwd / _bwd; 8: the layer-scale gradient without a division -- rscale of op_gemm_tn_grouped, op_transpose_scaled + the scale member of the op_transpose_batched descriptor, op_resid_bwd leaves gamma out of dbranch when g0 is asked for, op_gamma_grad_finish lost its gamma argument; rowdot is a [N / 128][M] matrix of partial sums written once each (no atomics); 9: row tables -- a residual branch that runs on the samples stochastic depth keeps reads and writes the FULL activation matrix through op_rows_map's table instead of through packed copies: x_rows of op_layernorm_fwd / op_layernorm_bwd, dout_rows of op_resid_bwd, resid_rows / resid_rows_total of op_gemm_nt and op_gemm_nt_grouped, op_rows_merge without `upd` copies the dropped samples' rows only; op_prof_reserve; 10: run-to-run identical gradients -- op_relpos_bias_bwd sums the table gradient in a fixed order from pair lists instead of scattering with atomics, op_relpos_bias_bwd_ids became op_relpos_bias_fold_ids, the separate dBias kernel of op_attn_bwd adds into one slab per batch chunk; (still 10, additive) op_live_ktiles + op_gemm_tn_grouped_lists: the weight gradients skip the K-tiles of samples stochastic depth dropped; (still 10, additive) op_live_mwindows + op_gemm_nt_grouped_windows: the input gradients skip their row blocks; (still 10, additive) op_live_mwindows_fwd + op_gemm_nt_grouped_windows_fwd: the forward GEMMs of a residual branch skip them too */
 const char* op_last_error(void);
 
 /* Live per-kernel-family timing with HIP events recorded on the launch stream (used by bench.py's `roofline`).
@@ -196,6 +196,26 @@ int op_live_mwindows(int64_t nseg, const float* const* ps, const int64_t* ps_str
 int op_gemm_nt_grouped_windows(int64_t nprob, const void* const* A, const int64_t* M, int64_t lda, const void* const* B, int64_t ldb,
                                void* const* C, int64_t ldc, int64_t N, int64_t K, const int32_t* windows, const int32_t* n_windows,
                                int64_t max_windows, int64_t max_row_stride, int64_t tune, void* stream);
+/* The same two for the FORWARD launches of a residual branch (q | k | v and out-proj + residual; wi_0 | wi_1 and down-projection +
+ * residual), whose rows of dropped samples the epilogue or a later kernel multiplies by 0.  Additive: op_abi_version() stays 10.
+ * op_live_mwindows_fwd: op_live_mwindows plus, per output, a source matrix out_src[o] (bf16, 16-byte aligned, row stride out_src_ld[o]
+ * % 8 == 0, not the output itself; null: +0 as above) whose rows are COPIED into the rows no window covers: the residual output takes
+ * the residual input, which is what the dense epilogue's fma(0, y, res) gives.  nout >= 1.
+ * op_gemm_nt_grouped_windows_fwd: B / bias hold 3 entries per problem, the weights [n_seg, K] and bias vectors (may be null) of the
+ * N / n_seg <= 3 column segments of its output (n_seg % 256 == 0).  epilogue 0: C = A W^T + b; epilogue 3: C = resid + rowscale[m /
+ * rows_per_sample] * gamma * (A W^T + b), m the row inside its problem (of a strided window too; rows * rows_per_sample < 2^32);
+ * resid (row stride ldr, max_row_stride * ldr < 2^23) / gamma / rowscale / rows_per_sample per problem as in op_gemm_nt_grouped; no
+ * branch output, no row table.  A listed row has the bits of the dense launch, no other row is written. */
+int op_live_mwindows_fwd(int64_t nseg, const float* const* ps, const int64_t* ps_stride, const int64_t* row0, const int64_t* S, const int64_t* B,
+                         const int64_t* wps, const int64_t* odd, const int64_t* seg_list, const int64_t* seg_prob, const int64_t* seg_base,
+                         int64_t nlist, int32_t* const* windows, int32_t* const* n_windows, const int64_t* max_windows, int64_t nout,
+                         void* const* out, const int64_t* out_ld, const int64_t* out_cols, const int64_t* out_rows,
+                         const void* const* out_src, const int64_t* out_src_ld, void* stream);
+int op_gemm_nt_grouped_windows_fwd(int64_t nprob, const void* const* A, const int64_t* M, int64_t lda, const void* const* B, int64_t ldb,
+                                   int64_t n_seg, const void* const* bias, void* const* C, int64_t ldc, const void* const* resid, int64_t ldr,
+                                   const void* const* gamma, const float* const* rowscale, const int64_t* rows_per_sample, int64_t N,
+                                   int64_t K, int epilogue, const int32_t* windows, const int32_t* n_windows, int64_t max_windows,
+                                   int64_t max_row_stride, int64_t tune, void* stream);
 /* `tune` (op_gemm_nt, op_gemm_tn, op_gemm_plan): per-call tuning word, 0 = what production uses.  The library keeps NO tuning
  * state, so every entry point is a pure function of its arguments; tests and tools select a kernel flavour with the call:
  * bits 0-1 tile (0 auto: a cost model picks 128x128 or 256x256 tiles, K-splits and the tail-rows split; 1 force 128x128;

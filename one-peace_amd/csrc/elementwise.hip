@@ -825,13 +825,14 @@ __global__ __launch_bounds__(256) void live_ktiles_kernel(const LiveTilesArgs a)
 // belongs to a kept sample.  A segment feeds up to two lists (the launch of its own rows and a grouped launch, with its problem index there); an
 // entry is two words: prob << 28 | (row - base), rows << 16 | row stride.  Grid: x = unit (all segments, then one workgroup per LIST that builds it: ordered ballot
 // compaction, segment by segment), y = MW_PIECE-row piece of the unit: the pieces of a unit that is NOT listed write +0 into their rows of
-// every output matrix (16-byte stores; the host checks cols % 8 == 0 and ld % 8 == 0).
+// every output matrix (16-byte stores; the host checks cols % 8 == 0 and ld % 8 == 0) -- or, for an output with a source matrix (the
+// residual output of a FORWARD branch: the dense epilogue gives fma(0, y, res) = res there), a copy of the source's rows.
 constexpr int MW_MAX_SEG = 4, MW_MAX_OUT = 4, MW_MAX_LIST = 4;
 constexpr int MW_PIECE = 16;  // rows a workgroup zero-fills: 64-row pieces left one workgroup per CU busy (1.4 TB/s on the FFN outputs)
 struct MWindowsArgs {
   int nseg, nout, nlist, nunits;
   struct { const float* ps; int64_t row0; int S, B, wps, odd, pstride, unit0, units; int list[2], prob[2]; int64_t base[2]; } seg[MW_MAX_SEG];
-  struct { bf16_t* ptr; int64_t ld; int cols; } out[MW_MAX_OUT];
+  struct { bf16_t* ptr; int64_t ld; int cols; const bf16_t* src; int64_t lds; } out[MW_MAX_OUT];  // src (forward, op_live_mwindows_fwd): rows to copy instead of +0
   struct { int* list; int* count; } lists[MW_MAX_LIST];
 };
 
@@ -909,8 +910,12 @@ __global__ __launch_bounds__(256) void live_mwindows_kernel(const MWindowsArgs a
   for (int o = 0; o < a.nout; ++o) {
     const int c8 = a.out[o].cols >> 3;
     bf16_t* base = a.out[o].ptr + (a.seg[i].row0 + r0) * a.out[o].ld;
+    const bf16_t* src = a.out[o].src;
+    if (src) src += (a.seg[i].row0 + r0) * a.out[o].lds;
     for (int r = wid; r < nrows; r += 4)  // a wave per row: 1 KiB contiguous per store instruction
-      for (int c = lane; c < c8; c += 64) *reinterpret_cast<uint4*>(base + (int64_t)r * a.out[o].ld + c * 8) = make_uint4(0u, 0u, 0u, 0u);
+      for (int c = lane; c < c8; c += 64)
+        *reinterpret_cast<uint4*>(base + (int64_t)r * a.out[o].ld + c * 8) =
+            src ? *reinterpret_cast<const uint4*>(src + (int64_t)r * a.out[o].lds + c * 8) : make_uint4(0u, 0u, 0u, 0u);
   }
 }
 
@@ -1378,11 +1383,11 @@ int op_live_ktiles(int64_t nseg, const float* const* ps, const int64_t* row0, co
 // Outputs (nout <= 4, may be 0): bf16 matrices of out_rows[o] rows PARALLEL to the row matrix (row stride out_ld[o], out_cols[o]
 // columns, both % 8 == 0); the rows of every unit (sample / tile) that is not listed are set to +0 in all of them.  A row that only a
 // neighbour's window reaches is zeroed here and written again by the GEMM, which runs later on the stream.
-int op_live_mwindows(int64_t nseg, const float* const* ps, const int64_t* ps_stride, const int64_t* row0, const int64_t* S, const int64_t* B,
-                     const int64_t* wps, const int64_t* odd, const int64_t* seg_list, const int64_t* seg_prob, const int64_t* seg_base, int64_t nlist,
-                     int32_t* const* windows,
-                     int32_t* const* n_windows, const int64_t* max_windows, int64_t nout, void* const* out, const int64_t* out_ld,
-                     const int64_t* out_cols, const int64_t* out_rows, void* stream) {
+static int live_mwindows_impl(int64_t nseg, const float* const* ps, const int64_t* ps_stride, const int64_t* row0, const int64_t* S, const int64_t* B,
+                              const int64_t* wps, const int64_t* odd, const int64_t* seg_list, const int64_t* seg_prob, const int64_t* seg_base, int64_t nlist,
+                              int32_t* const* windows,
+                              int32_t* const* n_windows, const int64_t* max_windows, int64_t nout, void* const* out, const int64_t* out_ld,
+                              const int64_t* out_cols, const int64_t* out_rows, const void* const* out_src, const int64_t* out_src_ld, void* stream) {
   OP_CHECK_ARG(nseg >= 1 && nseg <= MW_MAX_SEG && nlist >= 1 && nlist <= MW_MAX_LIST && nout >= 0 && nout <= MW_MAX_OUT,
                "live_mwindows: %lld segments (1 ... %d), %lld lists (1 ... %d), %lld outputs (0 ... %d)", (long long)nseg, MW_MAX_SEG,
                (long long)nlist, MW_MAX_LIST, (long long)nout, MW_MAX_OUT);
@@ -1425,10 +1430,38 @@ int op_live_mwindows(int64_t nseg, const float* const* ps, const int64_t* ps_str
     OP_CHECK_ARG(out[o] && ((uintptr_t)out[o] & 15) == 0 && out_cols[o] >= 8 && out_cols[o] % 8 == 0 && out_ld[o] % 8 == 0 && out_ld[o] >= out_cols[o] && out_rows[o] >= last_row &&
                  out_cols[o] < ((int64_t)1 << 31), "live_mwindows: output %d: null or not 16-byte aligned, cols / ld %% 8, or fewer than %lld rows", o, (long long)last_row);
     a.out[o].ptr = (bf16_t*)out[o]; a.out[o].ld = out_ld[o]; a.out[o].cols = (int)out_cols[o];
+    if (out_src && out_src[o]) {  // (the source has the output's rows and columns; it must not be the output itself or overlap it)
+      OP_CHECK_ARG(out_src_ld && ((uintptr_t)out_src[o] & 15) == 0 && out_src_ld[o] % 8 == 0 && out_src_ld[o] >= out_cols[o] && out_src[o] != out[o],
+                   "live_mwindows: source of output %d: not 16-byte aligned, ld %% 8 or ld < cols, or the output itself", o);
+      a.out[o].src = (const bf16_t*)out_src[o]; a.out[o].lds = out_src_ld[o];
+    }
   }
   hipLaunchKernelGGL(live_mwindows_kernel, dim3(units + (int)nlist, (int)((unit_rows + MW_PIECE - 1) / MW_PIECE)), dim3(256), 0, (hipStream_t)stream, a);
   OP_LAUNCH_CHECK();
   return OP_OK;
+}
+
+int op_live_mwindows(int64_t nseg, const float* const* ps, const int64_t* ps_stride, const int64_t* row0, const int64_t* S, const int64_t* B,
+                     const int64_t* wps, const int64_t* odd, const int64_t* seg_list, const int64_t* seg_prob, const int64_t* seg_base, int64_t nlist,
+                     int32_t* const* windows,
+                     int32_t* const* n_windows, const int64_t* max_windows, int64_t nout, void* const* out, const int64_t* out_ld,
+                     const int64_t* out_cols, const int64_t* out_rows, void* stream) {
+  return live_mwindows_impl(nseg, ps, ps_stride, row0, S, B, wps, odd, seg_list, seg_prob, seg_base, nlist, windows, n_windows, max_windows, nout,
+                            out, out_ld, out_cols, out_rows, nullptr, nullptr, stream);
+}
+
+// (additive: op_abi_version() stays 10) op_live_mwindows for the FORWARD launches of a residual branch (op_gemm_nt_grouped_windows_fwd):
+// the same lists by the same rule, and per output a source matrix out_src[o] (row stride out_src_ld[o] % 8 == 0, 16-byte aligned; null: +0
+// as above) whose rows are COPIED into the rows no window covers -- the residual output of the branch takes the residual input there,
+// which is what the dense epilogue's fma(0, y, res) gives for a dropped sample; a plain output (q | k | v, h0 | h1) takes +0.
+int op_live_mwindows_fwd(int64_t nseg, const float* const* ps, const int64_t* ps_stride, const int64_t* row0, const int64_t* S, const int64_t* B,
+                         const int64_t* wps, const int64_t* odd, const int64_t* seg_list, const int64_t* seg_prob, const int64_t* seg_base,
+                         int64_t nlist, int32_t* const* windows, int32_t* const* n_windows, const int64_t* max_windows, int64_t nout,
+                         void* const* out, const int64_t* out_ld, const int64_t* out_cols, const int64_t* out_rows,
+                         const void* const* out_src, const int64_t* out_src_ld, void* stream) {
+  OP_CHECK_ARG(nout >= 1 && out_src && out_src_ld, "live_mwindows_fwd: outputs with their source array (entries may be null)");
+  return live_mwindows_impl(nseg, ps, ps_stride, row0, S, B, wps, odd, seg_list, seg_prob, seg_base, nlist, windows, n_windows, max_windows, nout,
+                            out, out_ld, out_cols, out_rows, out_src, out_src_ld, stream);
 }
 
 }  // extern "C"

@@ -1075,7 +1075,7 @@ __global__ __launch_bounds__(256) void gemm256p_kernel(const GroupArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int SCHED = 3;
   static_assert(EPI == EPI_BIAS || epi_is_resid(EPI), "gemm256p_kernel: plain / bias and residual epilogues (epilogue_v)");
-  static_assert(!LIST || EPI == EPI_BIAS, "gemm256p_kernel: window lists go with the plain epilogue (input gradients)");
+  static_assert(!LIST || EPI != EPI_RESID_ROWS, "gemm256p_kernel: window lists go with the plain / bias and the residual epilogue, not with row tables");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 1, wn = wid & 1;
@@ -1261,16 +1261,22 @@ __global__ __launch_bounds__(256) void gemm256p_kernel(const GroupArgs p) {
       GemmArgs q;
       q.M = sel3(p.M, cur.prob); q.N = p.N; q.K = p.K; q.n_seg = p.n_seg; q.ldc = p.ldc; q.ldr = p.ldr; q.m_off = 0;
       q.C = sel3(p.C, cur.prob);
+      q.H0 = sel3(p.H0, cur.prob); q.H1 = sel3(p.H1, cur.prob);
+      q.resid = sel3(p.resid, cur.prob);
       if constexpr (LIST) {  // the window as a matrix of its own: `nrows` rows from the window's first row on, `rstride` rows apart
         q.C = (bf16_t*)q.C + (int64_t)cur.m0 * p.ldc; q.ldc = p.ldc * cur.rstride; q.M = cur.nrows;
-      } q.H0 = sel3(p.H0, cur.prob); q.H1 = sel3(p.H1, cur.prob);
-      q.resid = sel3(p.resid, cur.prob); q.gamma = sel3(p.gamma, cur.prob); q.rowscale = sel3(p.rowscale, cur.prob);
+        if constexpr (EPI == EPI_RESID) {  // the residual rows likewise; the multiplier of window row r is that of problem row m0 + r * rstride
+          q.resid += (int64_t)cur.m0 * p.ldr; q.ldr = p.ldr * cur.rstride; q.m_off = cur.m0; q.rstride = cur.rstride;
+          q.H0 = nullptr;  // (no branch output on a list: the entry refuses it)
+        }
+      }
+      q.gamma = sel3(p.gamma, cur.prob); q.rowscale = sel3(p.rowscale, cur.prob);
       q.rows_per_sample = sel3(p.rows_per_sample, cur.prob); q.alpha = p.alpha; q.rows = sel3(p.rows, cur.prob);
       q.bias[0] = q.bias[1] = q.bias[2] = nullptr;  // (unused: the tile's bias vector travels as an argument, see gemm_epilogue)
       // the tile lies in ONE weight segment (n_seg is a multiple of the tile width, checked at launch): kernel-argument table look-up
       const int segt = cur.n0 / p.n_seg;
       const bf16_t* bt = p.bias[cur.prob][segt];
-      epilogue_v<EPI>(q, acc, (LIST ? 0 : cur.m0) + wm * 128, cur.n0 + wn * 128, g, t, bt, true);
+      epilogue_v<EPI, false, LIST>(q, acc, (LIST ? 0 : cur.m0) + wm * 128, cur.n0 + wn * 128, g, t, bt, true);
     }
     zero_acc();
     cur = nxt;
@@ -2183,7 +2189,8 @@ int launch256p(const GroupArgs& ga, hipStream_t s, bool persistent = true) {
 }
 
 static int launch256p_any(const GroupArgs& ga, int epi, hipStream_t s, bool persistent) {
-  if (ga.wlist) return launch256p<EPI_BIAS, true>(ga, s, persistent);  // (the entry has checked: plain epilogue)
+  if (ga.wlist)  // (the entry has checked: plain / bias or residual epilogue, no row table)
+    return epi == EPI_RESID ? launch256p<EPI_RESID, true>(ga, s, persistent) : launch256p<EPI_BIAS, true>(ga, s, persistent);
   return op_with_int<EPI_BIAS, EPI_RESID, EPI_RESID_ROWS>(epi, [&](auto e) { return launch256p<decltype(e)::value>(ga, s, persistent); });
 }
 
@@ -2651,12 +2658,17 @@ static int gemm_nt_grouped_impl(int64_t nprob, const void* const* A, const int64
                                 const void* const* resid, int64_t ldr, const void* const* gamma, const float* const* rowscale,
                                 const int64_t* rows_per_sample, int64_t N, int64_t K, int epilogue, int64_t tune, const int* const* resid_rows,
                                 int64_t resid_rows_total, const int32_t* windows, const int32_t* n_windows, int64_t max_windows,
-                                int64_t max_row_stride, void* stream) {
+                                int64_t max_row_stride, void* stream, int64_t n_seg = 0, int wper = 2) {
+  // n_seg / wper (op_gemm_nt_grouped_windows_fwd): B and bias hold wper entries per problem, the weights (and bias vectors) of the
+  // N / n_seg column segments of its output; n_seg = 0: one weight per problem
   const GemmTune T = decode_tune(tune);
   if (windows)
-    OP_CHECK_ARG(n_windows && ((uintptr_t)windows & 7) == 0 && max_windows >= 1 && max_windows < ((int64_t)1 << 24) && epilogue == EPI_BIAS && !resid_rows &&
-                 max_row_stride >= 1 && max_row_stride < 65536 && max_row_stride * lda < ((int64_t)1 << 23) && max_row_stride * ldc < ((int64_t)1 << 23),
-                 "gemm_nt_grouped_windows: 8-byte aligned list, count, 1 <= max_windows < 2^24, plain epilogue, no row table, max_row_stride * lda (ldc) < 2^23");
+    OP_CHECK_ARG(n_windows && ((uintptr_t)windows & 7) == 0 && max_windows >= 1 && max_windows < ((int64_t)1 << 24) &&
+                 (epilogue == EPI_BIAS || epilogue == EPI_RESID) && !resid_rows && !h0 && !h1 &&
+                 max_row_stride >= 1 && max_row_stride < 65536 && max_row_stride * lda < ((int64_t)1 << 23) && max_row_stride * ldc < ((int64_t)1 << 23) &&
+                 (epilogue != EPI_RESID || (ldr % 8 == 0 && max_row_stride * ldr < ((int64_t)1 << 23))),
+                 "gemm_nt_grouped_windows: 8-byte aligned list, count, 1 <= max_windows < 2^24, plain or residual epilogue, no row table, no "
+                 "branch output, max_row_stride * lda (ldc, ldr) < 2^23");
   if (resid_rows) {  // (ABI 9) see op_gemm_nt: all problems or none, one row count for all the full matrices
     OP_CHECK_ARG(epilogue == EPI_RESID && resid_rows_total > 0 && ldr % 8 == 0 &&
                  (resid_rows_total * (ldc > ldr ? ldc : ldr) + N) * 2 < (int64_t)0xfff00000ll,
@@ -2675,6 +2687,9 @@ static int gemm_nt_grouped_impl(int64_t nprob, const void* const* A, const int64
     op_set_error("gemm_nt_grouped: shape N=%lld K=%lld not supported by the persistent kernel", (long long)N, (long long)K);
     return OP_ENOTSUP;
   }
+  if (n_seg == 0) n_seg = N;
+  OP_CHECK_ARG(n_seg > 0 && n_seg % 256 == 0 && N % n_seg == 0 && N / n_seg <= wper && wper <= 3,
+               "gemm_nt_grouped: column segments of %lld in N = %lld (whole 256-column tiles, at most %d)", (long long)n_seg, (long long)N, wper);
   GroupArgs ga;
   memset(&ga, 0, sizeof(ga));
   ga.nprob = (int)nprob;
@@ -2682,20 +2697,31 @@ static int gemm_nt_grouped_impl(int64_t nprob, const void* const* A, const int64
   double rows = 0;
   for (int i = 0; i < 3; ++i) {
     if (i < nprob) {
-      OP_CHECK_ARG(M[i] > 0 && A[i] && C[i] && B[i * 2], "gemm_nt_grouped: problem %d: empty or null operand", i);
+      OP_CHECK_ARG(M[i] > 0 && A[i] && C[i] && B[i * wper], "gemm_nt_grouped: problem %d: empty or null operand", i);
       if (M[i] * lda >= ((int64_t)1 << 30) || M[i] * ldc >= ((int64_t)1 << 30)) {
         op_set_error("gemm_nt_grouped: problem %d too large for 32-bit offsets", i);
         return OP_ENOTSUP;
       }
       ga.A[i] = (const bf16_t*)A[i]; ga.M[i] = (int)M[i];
-      ga.B[i][0] = (const bf16_t*)B[i * 2]; ga.B[i][1] = (const bf16_t*)B[i * 2 + 1];
-      ga.bias[i][0] = bias ? (const bf16_t*)bias[i * 2] : nullptr;
+      if (wper == 2) {
+        ga.B[i][0] = (const bf16_t*)B[i * 2]; ga.B[i][1] = (const bf16_t*)B[i * 2 + 1];
+        ga.bias[i][0] = bias ? (const bf16_t*)bias[i * 2] : nullptr;
+      } else {
+        for (int sgm = 0; sgm < (int)(N / n_seg); ++sgm) {
+          OP_CHECK_ARG(B[i * wper + sgm], "gemm_nt_grouped: problem %d: weight of column segment %d is null", i, sgm);
+          ga.B[i][sgm] = (const bf16_t*)B[i * wper + sgm];
+          ga.bias[i][sgm] = bias ? (const bf16_t*)bias[i * wper + sgm] : nullptr;
+        }
+      }
       ga.C[i] = C[i]; ga.H0[i] = h0 ? (bf16_t*)h0[i] : nullptr; ga.H1[i] = h1 ? (bf16_t*)h1[i] : nullptr;
       ga.resid[i] = resid ? (const bf16_t*)resid[i] : nullptr;
       if (epilogue == EPI_RESID) OP_CHECK_ARG(ga.resid[i], "gemm_nt_grouped: residual epilogue needs resid");
       ga.gamma[i] = gamma ? (const bf16_t*)gamma[i] : nullptr;
       ga.rowscale[i] = rowscale ? rowscale[i] : nullptr;
       ga.rows_per_sample[i] = rows_per_sample && rows_per_sample[i] > 0 ? (int)rows_per_sample[i] : 1;
+      if (windows && ga.rowscale[i])  // (the listed epilogue finds a row's sample by multiply-high without asking whether that is exact)
+        OP_CHECK_ARG((!rows_per_sample || rows_per_sample[i] < ((int64_t)1 << 31)) && M[i] * (int64_t)ga.rows_per_sample[i] < ((int64_t)1 << 32),
+                     "gemm_nt_grouped_windows: problem %d: rows * rows_per_sample >= 2^32", i);
       ga.rows[i] = resid_rows ? resid_rows[i] : nullptr;
       tiles += ceil_div(M[i], 256);
       rows += (double)M[i];
@@ -2708,7 +2734,7 @@ static int gemm_nt_grouped_impl(int64_t nprob, const void* const* A, const int64
   ga.wlist = windows; ga.wcount = n_windows; ga.max_rstride = (int)max_row_stride;
   ga.tiles_n = (int)(N / bn);
   ga.lda = lda; ga.ldb = ldb; ga.ldc = ldc; ga.ldr = ldr; ga.alpha = nullptr;
-  ga.n_seg = (int)N; ga.N = (int)N; ga.K = (int)K;
+  ga.n_seg = (int)n_seg; ga.N = (int)N; ga.K = (int)K;
   ga.gm = ga.tiles_n <= 8 ? 1 : 8;
   const int slot = op_prof_begin(0, 2.0 * rows * (double)N * (double)K, stream);
   // persistent (one workgroup per CU walks the tile list, K-tile stream continuous across tile boundaries) unless the caller asks
@@ -2745,6 +2771,26 @@ int op_gemm_nt_grouped_windows(int64_t nprob, const void* const* A, const int64_
   for (int i = 0; i < (int)nprob; ++i) B2[i * 2] = B[i];
   return gemm_nt_grouped_impl(nprob, A, M, lda, B2, ldb, nullptr, C, ldc, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, N, K,
                               EPI_BIAS, tune, nullptr, 0, windows, n_windows, max_windows, max_row_stride, stream);
+}
+
+// (additive: op_abi_version() stays 10) The FORWARD launches of a residual branch over a window list (op_live_mwindows_fwd builds it and
+// fills the rows no window covers): op_gemm_nt_grouped_windows with the operands of a forward launch.  B / bias: nprob x 3 entries, the
+// weights and bias vectors (may be null) of the N / n_seg <= 3 column segments of a problem's output (n_seg % 256 == 0: q | k | v with
+// n_seg = H, wi_0 | wi_1 with n_seg = F, one weight with n_seg = N).  epilogue 0: C = A W^T + b.  epilogue 3: C = resid + rowscale[m /
+// rows_per_sample] * gamma * (A W^T + b) with m the row INSIDE ITS PROBLEM -- of a strided window too --; resid (row stride ldr),
+// gamma, rowscale, rows_per_sample: per problem as in op_gemm_nt_grouped, no branch output (h0), no row table.  A listed row has the
+// bits of the dense launch; no other row of C is written.
+int op_gemm_nt_grouped_windows_fwd(int64_t nprob, const void* const* A, const int64_t* M, int64_t lda, const void* const* B, int64_t ldb,
+                                   int64_t n_seg, const void* const* bias, void* const* C, int64_t ldc, const void* const* resid, int64_t ldr,
+                                   const void* const* gamma, const float* const* rowscale, const int64_t* rows_per_sample, int64_t N,
+                                   int64_t K, int epilogue, const int32_t* windows, const int32_t* n_windows, int64_t max_windows,
+                                   int64_t max_row_stride, int64_t tune, void* stream) {
+  OP_CHECK_ARG(windows && n_windows && B && nprob >= 1 && nprob <= 3 && (epilogue == EPI_BIAS || epilogue == EPI_RESID) &&
+               (epilogue == EPI_BIAS || resid), "gemm_nt_grouped_windows_fwd: null list / weights / residual, 1..3 problems, epilogue 0 or 3");
+  OP_CHECK_ARG(n_seg > 0, "gemm_nt_grouped_windows_fwd: n_seg %lld", (long long)n_seg);
+  return gemm_nt_grouped_impl(nprob, A, M, lda, B, ldb, bias, C, ldc, nullptr, nullptr, epilogue == EPI_RESID ? resid : nullptr, ldr,
+                              epilogue == EPI_RESID ? gamma : nullptr, epilogue == EPI_RESID ? rowscale : nullptr, rows_per_sample, N, K,
+                              epilogue, tune, nullptr, 0, windows, n_windows, max_windows, max_row_stride, stream, n_seg, 3);
 }
 
 // C[M,N] (bf16, ldc) = A^T B with A [K, M] (lda) and B [K, N] (ldb) both row-major bf16: the weight-gradient GEMM

@@ -29,6 +29,7 @@ struct GemmArgs {
   int gm;             // 256x256 kernels: M-tiles per L2 group (tile order: gm M-tiles x all N-tiles, M fastest)
   int m_off;          // row index of A's first row in the caller's matrix (rowscale lookup of a tail-rows launch)
   const int* rows;    // EPI_RESID_ROWS: the row of resid / C that stands behind row m of the launch (-1: none); else unused
+  int rstride;        // epilogue_v<.., WIN>: rows of the caller's matrix between two rows of the launch (a strided window); else unused
 };
 
 __device__ __forceinline__ int xcd_remap(int b, int nwg) {
@@ -107,7 +108,9 @@ __device__ __forceinline__ void store_b128_padded(const u32x4& data, const u32x4
 // SCALED (fp8 operands, csrc/fp8.hip): the accumulator is dequantised by the row scale of the activation row and the row scale of the
 // weight row (= output column) before anything else:  y = acc * (sa[m] * sb[n]) (+ bias ...).  sa is indexed by the launch's row, sb by
 // the column inside the tile's weight segment (like the bias vector).
-template <int EPI, bool SCALED = false>
+// WIN (gemm256p_kernel over a window list, residual form): the launch's rows are a window of the caller's matrix -- row r is its row
+// m_off + r * rstride, and that row picks the multiplier.  C, resid and their leading dimensions already describe the window.
+template <int EPI, bool SCALED = false, bool WIN = false>
 __device__ __forceinline__ void epilogue_v(const GemmArgs& p, f32x4 (&acc)[2][4][8], int mrow0, int ncol0, int g, int t,
                                            const bf16_t* bias_of_tile = nullptr, const bool tile_bias = false, const float* sa = nullptr,
                                            const float* sb = nullptr) {
@@ -214,7 +217,9 @@ __device__ __forceinline__ void epilogue_v(const GemmArgs& p, f32x4 (&acc)[2][4]
     };
     // rowscale index of a row by multiply-high: exact while (rows + m_off) * rows_per_sample < 2^32 (else a true division)
     const unsigned rps = (unsigned)p.rows_per_sample;
-    const bool exact = p.rowscale && (uint64_t)((unsigned)(p.M + p.m_off)) * rps < (1ull << 32) && rps > 1;
+    const unsigned rstr = WIN ? (unsigned)p.rstride : 1u;
+    // (WIN: the host checks rows * rows_per_sample < 2^32 for every problem)
+    const bool exact = WIN ? rps > 1 : p.rowscale && (uint64_t)((unsigned)(p.M + p.m_off)) * rps < (1ull << 32) && rps > 1;
     const unsigned magic = exact ? 0xffffffffu / rps + 1u : 0u;
     // residual rows (and their row scales) in chunks of two 16-row fragments (8 rows per lane: 8 loads, 32 + 8 VGPRs), one chunk
     // ahead of the arithmetic: the first chunk's latency is exposed (together with the bias / gamma loads), the later ones hide
@@ -230,7 +235,8 @@ __device__ __forceinline__ void epilogue_v(const GemmArgs& p, f32x4 (&acc)[2][4]
           if constexpr (ROWS) dst[m2][r] = __builtin_amdgcn_raw_buffer_load_b128(rr, row_off(c * 2 + m2, r, ldr), 0, 0);
           else dst[m2][r] = __builtin_amdgcn_raw_buffer_load_b128(rr, voff_r, row * ldr * 2, 0);
           if (p.rowscale) {
-            const unsigned mc = (unsigned)(min(mrow0 + row + g * 4, p.M - 1) + p.m_off);
+            const unsigned mc = WIN ? (unsigned)min(mrow0 + row + g * 4, p.M - 1) * rstr + (unsigned)p.m_off
+                                    : (unsigned)(min(mrow0 + row + g * 4, p.M - 1) + p.m_off);
             rs[m2][r] = p.rowscale[exact ? __umulhi(mc, magic) : mc / rps];
           } else {
             rs[m2][r] = 1.f;

@@ -46,6 +46,9 @@ SIGNATURES = {
     "op_live_ktiles": (c_int, [I64, P, P, P, P, I64, P, P, P, P, P]),
     "op_live_mwindows": (c_int, [I64, P, P, P, P, P, P, P, P, P, P, I64, P, P, P, I64, P, P, P, P, P]),
     "op_gemm_nt_grouped_windows": (c_int, [I64, P, P, I64, P, I64, P, I64, I64, I64, P, P, I64, I64, I64, P]),
+    "op_live_mwindows_fwd": (c_int, [I64, P, P, P, P, P, P, P, P, P, P, I64, P, P, P, I64, P, P, P, P, P, P, P]),
+    "op_gemm_nt_grouped_windows_fwd": (c_int, [I64, P, P, I64, P, I64, I64, P, P, I64, P, I64, P, P, P, I64, I64, c_int, P, P, I64, I64,
+                                               I64, P]),
     "op_gemm_nt_batched": (c_int, [P, I64, I64, P, I64, I64, P, I64, P, I64, I64, I64, I64, I64, I64, P]),
     "op_audio_conv1_ln_gelu_fwd": (c_int, [P, I64, P, P, P, P, P, P, P, I64, I64, c_float, P]),
     "op_audio_conv1_ln_gelu_bwd_workspace_bytes": (I64, [I64]),
@@ -602,6 +605,11 @@ def live_mwindows(segs, lists, outs):
     the rows of `outs` the listed launches will not write.  segs: [(ps fp32 | None, row0, S, B[, ps stride = 1])], sample b has the multiplier ps[b * stride]; lists: per list the members
     [(segment index, problem index, row at which the problem's operand starts)], a segment in at most two lists; outs: bf16 matrices
     parallel to the row matrix.  Returns per list (windows int32 [2 * max] -- two words per entry --, count int32 [1]): views of ONE buffer, never read by the host."""
+    return _live_mwindows(segs, lists, outs, None)
+
+
+def _live_mwindows(segs, lists, outs, _srcs):
+    """live_mwindows (_srcs None) and live_mwindows_fwd."""
     ns, nl, no = len(segs), len(lists), len(outs)
     dev = outs[0].device if outs else next(q[0] for q in segs if q[0] is not None).device
     segs = [tuple(q) + (1,) * (5 - len(q)) for q in segs]
@@ -625,13 +633,61 @@ def live_mwindows(segs, lists, outs):
         assert ps is None or (ps.dtype == torch.float32 and ps.is_contiguous() and ps.numel() > (B - 1) * st and ps.device == buf.device)
     for o in outs:
         assert o.dtype == torch.bfloat16 and o.dim() == 2 and o.stride(1) == 1 and o.device == buf.device
-    _check(lib().op_live_mwindows(ns, _ptr_array([q[0] for q in segs], ns), i64([q[4] for q in segs]), i64([q[1] for q in segs]),
-                                  i64([q[2] for q in segs]), i64([q[3] for q in segs]), i64(wps), i64(odd), i64([v for r in ref for v in (r[0], r[3])]),
-                                  i64([v for r in ref for v in (r[1], r[4])]), i64([v for r in ref for v in (r[2], r[5])]), nl,
-                                  _ptr_array([q[0] for q in res], nl), _ptr_array([q[1] for q in res], nl), i64(sizes), no,
-                                  _ptr_array(outs, max(no, 1)), i64([o.stride(0) for o in outs] or [0]), i64([o.shape[1] for o in outs] or [0]),
-                                  i64([o.shape[0] for o in outs] or [0]), stream()), "op_live_mwindows")
+    args = (ns, _ptr_array([q[0] for q in segs], ns), i64([q[4] for q in segs]), i64([q[1] for q in segs]),
+            i64([q[2] for q in segs]), i64([q[3] for q in segs]), i64(wps), i64(odd), i64([v for r in ref for v in (r[0], r[3])]),
+            i64([v for r in ref for v in (r[1], r[4])]), i64([v for r in ref for v in (r[2], r[5])]), nl,
+            _ptr_array([q[0] for q in res], nl), _ptr_array([q[1] for q in res], nl), i64(sizes), no,
+            _ptr_array(outs, max(no, 1)), i64([o.stride(0) for o in outs] or [0]), i64([o.shape[1] for o in outs] or [0]),
+            i64([o.shape[0] for o in outs] or [0]))
+    if _srcs is None:
+        _check(lib().op_live_mwindows(*args, stream()), "op_live_mwindows")
+    else:  # (live_mwindows_fwd)
+        for o, q in zip(outs, _srcs):
+            assert q is None or (q.dtype == torch.bfloat16 and q.shape == o.shape and q.stride(1) == 1 and q.device == o.device)
+        _check(lib().op_live_mwindows_fwd(*args, _ptr_array(_srcs, no), i64([0 if q is None else q.stride(0) for q in _srcs]), stream()),
+               "op_live_mwindows_fwd")
     return res
+
+
+def live_mwindows_fwd(segs, lists, outs, srcs):
+    """live_mwindows for the FORWARD launches of a residual branch (gemm_nt_windows_fwd): the same lists; the rows of outs[o] that no window
+    covers get a copy of the same rows of srcs[o] (the residual output takes the residual input) or, with srcs[o] None, +0."""
+    assert len(outs) >= 1 and len(srcs) == len(outs)
+    return _live_mwindows(segs, lists, outs, list(srcs))
+
+
+def gemm_nt_windows_fwd(As, Wss, biases, outs, windows, n_seg, epilogue=EPI_BIAS, resids=None, gammas=None, rowscales=None,
+                        rows_per_sample=None, max_row_stride=1, tune=None):
+    """The rows of out_p = epilogue(A_p @ cat(Wss[p])^T + cat(biases[p])) that the entries of `windows` name, nothing else: the forward
+    form of gemm_nt_windows.  Wss[p] / biases[p]: the 1-3 weights [n_seg, K] (bias vectors or None) of the column segments of problem
+    p (q | k | v: n_seg = H; wi_0 | wi_1: n_seg = F).  EPI_RESID: out = resid + rowscale[m // rows_per_sample] * gamma * (...) with m
+    the row inside its problem.  Returns False (nothing launched) when the shape does not qualify."""
+    n = len(As)
+    nw = len(Wss[0])
+    K, N = As[0].shape[1], n_seg * nw
+    lda, ldb, ldc = As[0].stride(0), Wss[0][0].stride(0), outs[0].stride(0)
+    ldr = resids[0].stride(0) if resids else 0
+    assert all(a.stride(0) == lda and a.shape[1] == K and a.stride(1) == 1 for a in As) and all(o.stride(0) == ldc and o.shape[1] == N for o in outs)
+    assert all(len(ws) == nw and all(w.stride(0) == ldb and w.shape == (n_seg, K) for w in ws) for ws in Wss)
+    assert all(o.shape[0] == a.shape[0] for a, o in zip(As, outs)) and (not resids or all(r.stride(0) == ldr and r.shape == o.shape for r, o in zip(resids, outs)))
+    lst, cnt = windows
+    assert lst.dtype == torch.int32 and cnt.dtype == torch.int32 and lst.is_contiguous() and lst.numel() >= 2 and lst.data_ptr() % 8 == 0
+    if max_row_stride * max(lda, ldc, ldr) >= 1 << 23 or n_seg % 256 != 0:
+        return False
+    flatW = [w for ws in Wss for w in list(ws) + [None] * (3 - nw)]
+    flatb = [b for bs in (biases or [[None] * nw] * n) for b in list(bs) + [None] * (3 - nw)]
+    rps = (c_int64 * n)(*[(rows_per_sample[i] if rows_per_sample else 0) for i in range(n)])
+    rc = lib().op_gemm_nt_grouped_windows_fwd(n, _ptr_array(As, n), (c_int64 * n)(*[a.shape[0] for a in As]), lda, _ptr_array(flatW, 3 * n), ldb,
+                                              n_seg, _ptr_array(flatb, 3 * n), _ptr_array(outs, n), ldc, _ptr_array(resids, n), ldr,
+                                              _ptr_array(gammas, n), _ptr_array(rowscales, n), rps, N, K, epilogue, ptr(lst), ptr(cnt),
+                                              lst.numel() // 2, max_row_stride, TUNE.gemm() if tune is None else int(tune), stream())
+    if rc == -95:
+        return False
+    _check(rc, "op_gemm_nt_grouped_windows_fwd")
+    for a in As:  # (the dense launch's bytes, as in gemm_nt_windows)
+        GEMM_ALGO_BYTES[0] += 2 * (a.shape[0] * K + N * K + (a.shape[0] * N if resids else 0)) + 2 * a.shape[0] * N
+    GEMM_ALGO_BYTES[1] += 1
+    return True
 
 
 def gemm_nt_windows(As, Ws, outs, windows, max_row_stride=1, tune=None):

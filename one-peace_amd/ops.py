@@ -348,6 +348,48 @@ def _dgrad_listed(As, Ws, outs, windows, segs):
     return hip.gemm_nt_windows(As, Ws, outs, windows, max([sg.S for sg in segs if hip.mwindow_rule(sg.S)[1]] or [1]))
 
 
+# The FORWARD GEMMs of such a branch (q|k|v, out-proj + residual; wi_0|wi_1, down-projection + residual) multiply every row of a dropped
+# sample, and the epilogue or a later kernel multiplies the result by ps = 0.  "1": they run over the same kind of window lists
+# (hip.live_mwindows_fwd: one launch per branch builds the list and FILLS the rows no window covers -- +0 in q|k|v and h0|h1, a copy of
+# the residual input in the branch output, which is what fma(0, y, res) gives).  A listed row is the dense launch's row (same operands,
+# same K order, same epilogue); a -0 element of a dropped sample's residual stays -0 where the dense epilogue can give +0, and a non-finite
+# y in a dropped row no longer becomes NaN: equal as numbers, as the backward lists.  The row kernels and attention stay dense and read
+# zeros for a dropped sample.  "0": the dense launches (A/B, tests).  Independent of SKIP_ZERO_DGRAD / SKIP_ZERO_BACKWARD.
+SKIP_ZERO_FWD = os.environ.get("ONEPEACE_SKIP_ZERO_FWD", "1") != "0"
+_dense_fwd_plans = {}
+
+
+def _dense_fwd_sums_k_in_one_piece(M, N, K, epilogue, has_bias, device):
+    """_dense_dgrad_sums_k_in_one_piece for a forward launch of hip.gemm_nt with its own epilogue."""
+    scratch = hip.splitk_scratch(M, N, K, epilogue, device)
+    ws = scratch.numel() if scratch is not None else 0
+    key = (M, N, K, epilogue, has_bias, ws, hip.TUNE.gemm())
+    if key not in _dense_fwd_plans:
+        _, splits, _, tail = hip.gemm_plan(M, N, K, epilogue, has_bias, ws)
+        _dense_fwd_plans[key] = splits == 1 and (tail == 0 or hip.gemm_plan(tail, N, K, epilogue, has_bias, ws)[1] == 1)
+    return _dense_fwd_plans[key]
+
+
+def _fwd_windows_apply(segs, nlists, nouts, dense, device, flags=True):
+    """Do window lists serve the forward launches of a branch?  Decided from shapes and flags alone (the forward and its recomputation
+    agree): switched on, `flags` (the caller's: no row tables, no branch output, no fp8, no padded segment), some segment has
+    multipliers, shapes the persistent kernel and the list format take, and no dense launch ([(M, N, K, epilogue, has_bias)], the
+    hip.gemm_nt launches the lists replace) that splits K.  segs: [(ps, row0, S, B, ps stride)]."""
+    if not SKIP_ZERO_FWD or not flags or all(q[0] is None for q in segs) or len(segs) > 4 or nlists > 4 or nouts > 4:
+        return False
+    if any(ps is not None and (ps.dtype != torch.float32 or not ps.is_contiguous() or ps.numel() <= (B - 1) * st) for ps, _, _, B, st in segs):
+        return False
+    if any(S * B >= 1 << 27 or row0 + S * B + 256 * 64 >= 1 << 28 for _, row0, S, B, _ in segs):
+        return False
+    mrs = max([q[2] for q in segs if hip.mwindow_rule(q[2])[1]] or [1])
+    for M, N, K, epi, has_bias in dense:
+        if N % 256 != 0 or K % 64 != 0 or K < 128 or M * max(N, K) >= 1 << 30 or mrs * max(N, K) >= 1 << 23:
+            return False
+        if not _dense_fwd_sums_k_in_one_piece(M, N, K, epi, has_bias, device):
+            return False
+    return True
+
+
 class _WgradQueue:
     """Weight-gradient GEMMs that accumulate into flat gradient views, collected while a layer's backward runs (FFN branch
     first, then the attention branch, which flushes): launched alone each of them has 36 ... 288 output tiles for 256 CUs and
@@ -971,17 +1013,31 @@ class StreamSeg:
         return self.bias.frag if self.bias is not None and self.S <= limit else None
 
 
-def _attn_forward(x2, P, segs, heads, scale, rowscale, rps, keep, want_y=True, xmap=None, out=None):
+def _attn_forward(x2, P, segs, heads, scale, rowscale, rps, keep, want_y=True, xmap=None, out=None, listed=False):
     """x_mid = x + rowscale * g1 * out_proj(subLN(attention(LN1(x))))  on the packed rows x2 [N, H]: LayerNorm, the fused q|k|v
     projection, the sub-LayerNorm and the output projection run over ALL rows in one launch each, the attention core per
     segment.  rowscale: fp32 drop-path multipliers indexed by row // rps (None = 1).  want_y: also write the branch output y1
     (only the gradient of gamma_1 needs it).  xmap (hip.KeptRows.rowmap) + out: x2 is the FULL matrix, the branch runs on its rows
-    xmap[r] and writes x_mid for them into `out` (a full matrix; the other rows are the caller's)."""
+    xmap[r] and writes x_mid for them into `out` (a full matrix; the other rows are the caller's).  listed (the caller's flags: no
+    `kept`, gamma_1's gradient does not need y1): the two GEMMs may run over ONE window list of all rows (SKIP_ZERO_FWD)."""
     H = x2.shape[1]
     xln1, mean1, rstd1 = hip.layernorm_fwd(x2, P["ln1_w"], P["ln1_b"], want_stats=keep, x_rows=xmap)
-    if H % 128 == 0:
-        Nr = xln1.shape[0]
-        full = _qkv_rows_that_fill_whole_rounds(Nr, 3 * H) if QKV_ROUND_SPLIT else Nr
+    Nr = xln1.shape[0]
+    full = _qkv_rows_that_fill_whole_rounds(Nr, 3 * H) if QKV_ROUND_SPLIT and H % 128 == 0 else Nr
+    win, mrs, qkv, x_mid = None, 1, None, None
+    if (listed and rowscale is not None and xmap is None and out is None and not (keep and want_y) and H % 256 == 0 and Nr % rps == 0
+            and sum(sg.rows for sg in segs) == Nr and all(sg.S % rps == 0 and sg.row0 % rps == 0 for sg in segs)):
+        wsegs = [(rowscale[sg.row0 // rps:], sg.row0, sg.S, sg.B, sg.S // rps) for sg in segs]
+        dense = [(m, 3 * H, H, hip.EPI_BIAS, True) for m in ((full, Nr - full) if full < Nr else (Nr,))] + [(Nr, H, H, hip.EPI_RESID, True)]
+        if _fwd_windows_apply(wsegs, 1, 2, dense, x2.device, flags=not any(sg.pad for sg in segs)):
+            qkv = torch.empty(Nr, 3 * H, dtype=x2.dtype, device=x2.device)
+            x_mid = torch.empty_like(x2)
+            win = hip.live_mwindows_fwd(wsegs, [[(i, 0, 0) for i in range(len(segs))]], [qkv, x_mid], [None, x2])[0]
+            mrs = max([sg.S for sg in segs if hip.mwindow_rule(sg.S)[1]] or [1])
+    if win is not None and hip.gemm_nt_windows_fwd([xln1], [[P["wq"], P["wk"], P["wv"]]], [[P["bq"], None, P["bv"]]], [qkv], win, H,
+                                                   max_row_stride=mrs):
+        pass  # (one listed launch over all rows instead of the whole-rounds + tail pair)
+    elif H % 128 == 0:
         if full < Nr:  # (689.8 / 689.7 -> 687.3 / 687.0 ms on the headline step, same box: profiles/r5_experiments.md section 12)
             qkv = torch.empty(Nr, 3 * H, dtype=x2.dtype, device=x2.device)
             for lo, hi in ((0, full), (full, Nr)):
@@ -1007,8 +1063,10 @@ def _attn_forward(x2, P, segs, heads, scale, rowscale, rps, keep, want_y=True, x
     else:
         aln, mean_a, rstd_a = attn, None, None
     y1 = torch.empty_like(xln1) if keep and want_y else None
-    x_mid = hip.gemm_nt(aln, [P["wo"]], [P["bo"]], epilogue=hip.EPI_RESID, resid=x2, gamma=P["g1"], rowscale=rowscale,
-                        rows_per_sample=rps, h0=y1, out=out, resid_rows=xmap)
+    if win is None or not hip.gemm_nt_windows_fwd([aln], [[P["wo"]]], [[P["bo"]]], [x_mid], win, H, epilogue=hip.EPI_RESID, resids=[x2],
+                                                  gammas=[P["g1"]], rowscales=[rowscale], rows_per_sample=[rps], max_row_stride=mrs):
+        x_mid = hip.gemm_nt(aln, [P["wo"]], [P["bo"]], epilogue=hip.EPI_RESID, resid=x2, gamma=P["g1"], rowscale=rowscale,
+                            rows_per_sample=rps, h0=y1, out=out, resid_rows=xmap)
     if not keep:
         return x_mid, None
     acts = dict(xln1=xln1, mean1=mean1, rstd1=rstd1, qkv=qkv, attn=attn, aln=aln, mean_a=mean_a, rstd_a=rstd_a, y1=y1)
@@ -1202,7 +1260,8 @@ class AttnBranchFn(torch.autograd.Function):
                                     xmap=kept.rowmap(), out=x_mid)
             hip.rows_merge(x_full, None, kept, out=x_mid)  # (the dropped samples' rows: copied)
         else:
-            x_mid, acts = _attn_forward(x2, P, segs, heads, scale, rowscale, rps, keep, want_y=needs["g1"] and not ctx.dg_fused)
+            x_mid, acts = _attn_forward(x2, P, segs, heads, scale, rowscale, rps, keep, want_y=needs["g1"] and not ctx.dg_fused,
+                                        listed=kept is None and ctx.dg_fused)
             if kept is not None:
                 x_mid = hip.rows_merge(x_full, x_mid, kept)
         ctx.kept, ctx.mapped = kept, mapped
@@ -1247,7 +1306,7 @@ class AttnBranchFn(torch.autograd.Function):
                     A["aln"] = hip.layernorm_fwd(A["attn"], P["aln_w"], P["aln_b"])[0]
         else:  # recompute (the reference's checkpoint_activations behaviour)
             _, A = _attn_forward(x2, P, segs, heads, scale, rowscale, rps, True, want_y=not ctx.dg_fused, xmap=xmap,
-                                 out=torch.empty_like(x2) if mapped else None)
+                                 out=torch.empty_like(x2) if mapped else None, listed=kept is None and ctx.dg_fused)
         if not dx_mid.is_contiguous():
             dx_mid = dx_mid.contiguous()
         dx_full = dx_mid
@@ -1391,13 +1450,15 @@ class FfnBranchMultiFn(torch.autograd.Function):
     params: ln2_w, ln2_b, g2, then (w0, w1, fln_w, fln_b, w2, b2) per segment."""
 
     @staticmethod
-    def _compute(x2, segs, pss, params, keep, want_y, grad=None, xmap=None):
+    def _compute(x2, segs, pss, params, keep, want_y, grad=None, xmap=None, listed=False):
         """grad: the pass belongs to a training step (default: keep).  The GeGLU form is chosen by THAT, not by `keep`: with
         checkpoint_activations the forward (keep = False) and its recomputation in backward (keep = True) must run the same kernels, or
         the LayerNorm(F) statistics the gradients use are not those of the forward output.  No-grad inference keeps the fused
         GeGLU epilogue (one store instead of three; h0 / h1 rounded to bf16 only in the split form: a bf16-level train / eval difference).
         xmap (hip.KeptRows.rowmap, not with the fp8 FFN): x2 is the FULL matrix, the branch runs on its rows xmap[r]; the returned
-        `out` is a full matrix in which the rows of the kept samples are written (the others are the caller's)."""
+        `out` is a full matrix in which the rows of the kept samples are written (the others are the caller's).
+        listed (the caller's flags: no `kept`, gamma_2's gradient does not need y2): the split form's wi_0 | wi_1 launches become ONE
+        grouped launch over a window list, which also serves the grouped down-projection (SKIP_ZERO_FWD)."""
         nseg = len(segs)
         shared = dict(zip(FFN_SHARED, params[:3]))
         own = [dict(zip(FFN_OWN, params[3 + 6 * i:9 + 6 * i])) for i in range(nseg)]
@@ -1427,13 +1488,24 @@ class FfnBranchMultiFn(torch.autograd.Function):
         mean_f = torch.empty(N, dtype=torch.float32, device=dev) if (keep or split) and has_fln else None
         rstd_f = torch.empty(N, dtype=torch.float32, device=dev) if (keep or split) and has_fln else None
         L = hip.lib()
+        rs = [slice(sg.row0, sg.end) for sg in segs]
+        win, mrs, out, listed_up = None, 1, None, False
+        if listed and split and not fp8 and xmap is None and not (keep and want_y) and nseg <= 3 and H % 256 == 0:
+            wsegs = [(ps, sg.row0, sg.S, sg.B, 1) for ps, sg in zip(pss, segs)]
+            dense = [(sg.rows, 2 * Fd, H, hip.EPI_BIAS, False) for sg in segs] + ([(segs[0].rows, H, Fd, hip.EPI_RESID, True)] if nseg == 1 else [])
+            if _fwd_windows_apply(wsegs, 1, 2, dense, dev, flags=not any(sg.pad for sg in segs)):
+                out = torch.empty_like(x2)
+                win = hip.live_mwindows_fwd(wsegs, [[(i, i, sg.row0) for i, sg in enumerate(segs)]], [hh, out], [None, x2])[0]
+                mrs = max([sg.S for sg in segs if hip.mwindow_rule(sg.S)[1]] or [1])
+                listed_up = hip.gemm_nt_windows_fwd([xln2[r] for r in rs], [[P["w0"], P["w1"]] for P in own], None, [hh[r] for r in rs], win, Fd,
+                                                    max_row_stride=mrs)
         for sg, P in zip(segs, own):
             r = slice(sg.row0, sg.end)
             if split:
                 if fp8:
                     w01q, w01s = _fp8_weight_pair(P["w0"], P["w1"])
                     hip.gemm_nt_fp8(xq[r], xs[r], [w01q], [w01s], out=hh[r])
-                else:
+                elif not listed_up:
                     hip.gemm_nt(xln2[r], [P["w0"], P["w1"]], n_seg=Fd, N=2 * Fd, out=hh[r])
                 hip.ln_geglu_fwd(h0[r], h1[r], P["fln_w"], P["fln_b"], out=gln[r], mean=mean_f[r], rstd=rstd_f[r],
                                  q8=(gq[r], gs[r]) if fp8 else None)
@@ -1450,8 +1522,8 @@ class FfnBranchMultiFn(torch.autograd.Function):
                                               hip.ptr(mean_f[r]) if keep else None, hip.ptr(rstd_f[r]) if keep else None, sg.rows, Fd, 1e-5, 0,
                                               hip.DT_BF16, None, hip.stream()), "op_layernorm_fwd")
         y2 = torch.empty(N, H, dtype=dt, device=dev) if keep and want_y else None
-        out = torch.empty_like(x2)  # (with xmap: the full matrix)
-        rs = [slice(sg.row0, sg.end) for sg in segs]
+        if out is None:
+            out = torch.empty_like(x2)  # (with xmap: the full matrix)
         if fp8:  # one fp8 launch per modality (the grouped persistent launch is bf16 only)
             if gq is None:
                 gq, gs = hip.quant_fp8_rows(gln)
@@ -1462,6 +1534,11 @@ class FfnBranchMultiFn(torch.autograd.Function):
             acts = dict(xln2=xln2, mean2=mean2, rstd2=rstd2, h0=h0, h1=h1, gln=gln, mean_f=mean_f, rstd_f=rstd_f, y2=y2) if keep else None
             return out, acts
         tabs = [xmap[r] for r in rs] if xmap is not None else None  # (row tables: every problem writes ITS rows of the shared full matrix)
+        if win is not None and hip.gemm_nt_windows_fwd([gln[r] for r in rs], [[P["w2"]] for P in own], [[P["b2"]] for P in own], [out[r] for r in rs],
+                                                       win, H, epilogue=hip.EPI_RESID, resids=[x2[r] for r in rs], gammas=[shared["g2"]] * nseg,
+                                                       rowscales=list(pss), rows_per_sample=[sg.S for sg in segs], max_row_stride=mrs):
+            acts = dict(xln2=xln2, mean2=mean2, rstd2=rstd2, h0=h0, h1=h1, gln=gln, mean_f=mean_f, rstd_f=rstd_f, y2=y2) if keep else None
+            return out, acts
         grouped = nseg > 1 and hip.gemm_nt_grouped(
             [gln[r] for r in rs], [P["w2"] for P in own], biases=[P["b2"] for P in own],
             outs=[out[r] for r in rs] if tabs is None else [out] * nseg, epilogue=hip.EPI_RESID,
@@ -1493,7 +1570,7 @@ class FfnBranchMultiFn(torch.autograd.Function):
         ctx.dg_fused = need_grad and dgamma_from_wgrad_ok([sg.rows for sg in segs], params[2], w2s, b2s, bool(needs[2]),
                                                            [bool(needs[3 + 6 * i + 4]) for i in range(nseg)])
         out, acts = FfnBranchMultiFn._compute(x2, segs, pss, params, keep, bool(needs[2]) and not ctx.dg_fused, grad=bool(int(save_acts) & 2),
-                                              xmap=kept.rowmap() if mapped else None)
+                                              xmap=kept.rowmap() if mapped else None, listed=kept is None and ctx.dg_fused)
         if mapped:
             hip.rows_merge(x_full, None, kept, out=out)  # (the dropped samples' rows: copied)
         elif kept is not None:
@@ -1544,7 +1621,7 @@ class FfnBranchMultiFn(torch.autograd.Function):
                         r = slice(sg.row0, sg.end)
                         hip.ln_geglu_fwd(A["h0"][r], A["h1"][r], P["fln_w@%d" % i], P["fln_b@%d" % i], out=A["gln"][r], want_stats=False)
         else:  # recompute (the reference's checkpoint_activations behaviour)
-            _, A = FfnBranchMultiFn._compute(x2, segs, pss, params, True, not ctx.dg_fused, xmap=xmap)
+            _, A = FfnBranchMultiFn._compute(x2, segs, pss, params, True, not ctx.dg_fused, xmap=xmap, listed=kept is None and ctx.dg_fused)
         if not dout.is_contiguous():
             dout = dout.contiguous()
         dout_full = dout
