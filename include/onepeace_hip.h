@@ -343,7 +343,8 @@ int op_colsum_segments(const void* x, void* out0, void* out1, void* out2, void* 
  * op_gamma_grad_finish multiplies with the last Linear's bias when dgamma is taken from the weight gradient instead of from y.
  * (ABI 8) With g0 != NULL (an alternative to y + dgamma) dbranch = rowscale*dout, WITHOUT gamma: the weight-gradient launch applies
  * gamma to its output rows (op_gemm_tn_grouped: rscale) and the input-gradient GEMM reads a gamma-scaled weight copy
- * (op_transpose_scaled), so that the layer-scale gradient needs no division by gamma. */
+ * (op_transpose_scaled), so that the layer-scale gradient needs no division by gamma.
+ * M = 0 (valid pointers): the sums over no rows are zero -- g0 and the non-accumulating dgamma / dbias are cleared, nothing else is written. */
 int64_t op_resid_bwd_workspace_bytes(int64_t N);
 int op_resid_bwd(const void* dout, const void* y, const void* gamma, const float* rowscale, int64_t rows_per_sample,
                  void* dbranch, void* dgamma, void* dbias, float* g0, void* workspace, int64_t M, int64_t N, int accumulate,

@@ -989,8 +989,12 @@ int op_resid_bwd(const void* dout, const void* y, const void* gamma, const float
   OP_CHECK_ARG(!dgamma || y, "resid_bwd: dgamma needs y");
   OP_CHECK_ARG(!(dgamma && g0), "resid_bwd: g0 (dbranch without gamma) and dgamma (from y) are alternatives");
   OP_CHECK_ARG(!(dgamma || dbias || g0) || workspace, "resid_bwd: dgamma/dbias/g0 requested without workspace");
-  if (M == 0) {
+  if (M == 0) {  // the sum over no rows is zero: g0 and the non-accumulating dgamma / dbias are cleared, accumulating ones stay
     if (g0) (void)hipMemsetAsync(g0, 0, (size_t)N * sizeof(float), (hipStream_t)stream);
+    if (!accumulate) {
+      if (dgamma) (void)hipMemsetAsync(dgamma, 0, (size_t)N * sizeof(bf16_t), (hipStream_t)stream);
+      if (dbias) (void)hipMemsetAsync(dbias, 0, (size_t)N * sizeof(bf16_t), (hipStream_t)stream);
+    }
     return OP_OK;
   }
   hipStream_t s = (hipStream_t)stream;

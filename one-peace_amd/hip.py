@@ -791,13 +791,20 @@ def transpose_batched(table, n, total_tiles):
     _check(lib().op_transpose_batched(ptr(table), n, total_tiles, stream()), "op_transpose_batched")
 
 
+def _ptr_rows(t, stand_in):
+    """ptr(t) for an operand of M rows.  An EMPTY tensor (M = 0) has a null address, which the entry points refuse before they look at M:
+    the address of `stand_in` (the launch's workspace) goes in its place -- no row of it is read or written."""
+    return ptr(stand_in) if t is not None and t.numel() == 0 else ptr(t)
+
+
 def colsum(x, y=None, rowscale=None, rows_per_sample=0, mul=None, out=None, accumulate=False, out_dtype=torch.bfloat16):
+    """M = 0: the sum over no rows -- zeros, or `out` untouched when accumulating."""
     M, N = x.shape
     if out is None:
         out = torch.empty(N, dtype=out_dtype, device=x.device)
         accumulate = False
     ws = workspace(lib().op_colsum_workspace_bytes(N), x.device, "colsum")
-    _check(lib().op_colsum(ptr(x), ptr(y), ptr(rowscale), rows_per_sample, ptr(mul), ptr(out), ptr(ws), M, N,
+    _check(lib().op_colsum(_ptr_rows(x, ws), _ptr_rows(y, ws), _ptr_rows(rowscale, ws), rows_per_sample, ptr(mul), ptr(out), ptr(ws), M, N,
                            int(accumulate), _dt(out), stream()), "op_colsum")
     return out
 
@@ -811,7 +818,7 @@ def colsum_segments(x, seg_cols, outs=None, accumulate=False):
         accumulate = False
     o = list(outs) + [None] * (3 - len(outs))
     ws = workspace(lib().op_colsum_workspace_bytes(N), x.device, "colsum")
-    _check(lib().op_colsum_segments(ptr(x), ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(ws), M, n_seg, seg_cols, int(accumulate),
+    _check(lib().op_colsum_segments(_ptr_rows(x, ws), ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(ws), M, n_seg, seg_cols, int(accumulate),
                                     stream()), "op_colsum_segments")
     return outs
 
@@ -832,12 +839,13 @@ def resid_bwd(dout, y=None, gamma=None, rowscale=None, rows_per_sample=0, dgamma
     if dbias is True:
         dbias = torch.empty(N, dtype=dout.dtype, device=dout.device)
     ws = None
-    if dgamma is not None or dbias is not None or g0 is not None:
+    if dgamma is not None or dbias is not None or g0 is not None or M == 0:
         ws = workspace(lib().op_resid_bwd_workspace_bytes(N), dout.device, "resid")
     assert g0 is None or (g0.dtype == torch.float32 and g0.is_contiguous() and g0.numel() == N)
-    _check(lib().op_resid_bwd(ptr(dout), ptr(y if dgamma is not None else None), ptr(gamma), ptr(rowscale), rows_per_sample,
-                              ptr(out), ptr(dgamma), ptr(dbias), ptr(g0), ptr(ws), M, N, int(accumulate), ptr(dout_rows), stream()),
-           "op_resid_bwd")
+    # (M = 0: g0 and the non-accumulating dgamma / dbias come back as zeros, the sums over no rows)
+    _check(lib().op_resid_bwd(_ptr_rows(dout, ws), _ptr_rows(y if dgamma is not None else None, ws), ptr(gamma), _ptr_rows(rowscale, ws),
+                              rows_per_sample, _ptr_rows(out, ws), ptr(dgamma), ptr(dbias), ptr(g0), ptr(ws), M, N, int(accumulate),
+                              _ptr_rows(dout_rows, ws), stream()), "op_resid_bwd")
     return out, dgamma, dbias
 
 

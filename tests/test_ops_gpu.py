@@ -10,7 +10,14 @@ The LayerNorm tests here (test_layernorm_*, test_ln_geglu_*, the x_rows tests) s
 second row and use the same aggregate gates.  The per-element check of those kernels against fp64 -- the persistent row loop at three
 trips, mean and rstd as fp32 numbers, `add`, `accumulate`, the row table, the fp8 copies and the non-temporal variants, outputs in
 guarded buffers -- is tests/test_ln_fp64_gpu.py (reference, derived budget and cases: tests/ln_ref.py, checked on the CPU by
-tests/test_ln_ref_cpu.py)."""
+tests/test_ln_ref_cpu.py).
+
+The row-wise backward tests here (test_transpose, test_colsum_and_scale_rows, test_resid_bwd_one_pass, test_colsum_segments_*,
+test_geglu_bwd, test_resid_bwd_g0_and_gamma_grad_finish, test_gamma_grad_finish_with_three_weight_sets_sharing_gamma) stay at 4100 rows and below -- `parts` under its clamp of 256, 16 rows per wave, one trip of every grid-stride loop -- and
+gate norms over all columns, so that one wrong column or row passes.  The per-element check of those kernels against fp64 -- the row
+loops past the clamp with their odd tails, the second grid-stride trip, every combination of op_resid_bwd's optional arguments, the
+GELU tails, odd leading dimensions, M = 0, a NaN-filled workspace, outputs in guarded buffers -- is tests/test_rows_fp64_gpu.py
+(reference, derived budget and cases: tests/rows_ref.py, checked on the CPU by tests/test_rows_ref_cpu.py)."""
 import math
 
 import pytest
