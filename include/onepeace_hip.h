@@ -111,7 +111,9 @@ int op_gemm_nt_batched(const void* A, int64_t lda, int64_t stride_a, const void*
  *   y[r][c] = GELU(LN_C(bf16(sum_j w0[c][j] * wav[stride * r + j] (+ b0[c]))))        rows x C bf16, C <= 512, C % 8 == 0
  * mean / rstd [rows] fp32 are kept for the backward, which RECOMPUTES the row from its ten samples and returns the parameter gradients
  * (dw0 [C, 10], db0 [C], dlnw [C], dlnb [C]; bf16; nullable except dw0; overwritten or accumulated) -- the 2.1 GB convolution output
- * of the headline batch is never written, re-read or kept.  workspace: op_audio_conv1_ln_gelu_bwd_workspace_bytes(C). */
+ * of the headline batch is never written, re-read or kept.  workspace: op_audio_conv1_ln_gelu_bwd_workspace_bytes(C).
+ * rows = 0 (valid pointers): the forward writes nothing; the backward's sums over no rows are zero -- non-accumulating gradients are
+ * cleared, accumulating ones stay; both return OP_OK. */
 int op_audio_conv1_ln_gelu_fwd(const void* wav, int64_t stride, const void* w0, const void* b0, const void* lnw, const void* lnb, void* y,
                                float* mean, float* rstd, int64_t rows, int64_t C, float eps, void* stream);
 int64_t op_audio_conv1_ln_gelu_bwd_workspace_bytes(int64_t C);

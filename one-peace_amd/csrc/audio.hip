@@ -233,13 +233,23 @@ int64_t op_audio_conv1_ln_gelu_bwd_workspace_bytes(int64_t C) { return (int64_t)
 
 // Gradients of op_audio_conv1_ln_gelu_fwd's parameters from dy [rows, C] (the waveform gets none): dw0 [C, 10], db0 [C] (nullable),
 // dlnw [C], dlnb [C] (nullable), all bf16, overwritten or accumulated.  workspace: op_audio_conv1_ln_gelu_bwd_workspace_bytes(C).
+// rows == 0 (valid pointers): non-accumulating outputs are cleared, accumulating ones stay, nothing is launched.
 int op_audio_conv1_ln_gelu_bwd(const void* dy, const void* wav, int64_t stride, const void* w0, const void* b0, const void* lnw, const void* lnb,
                                const float* mean, const float* rstd, void* dw0, void* db0, void* dlnw, void* dlnb, void* workspace,
                                int64_t rows, int64_t C, int accumulate, void* stream) {
   OP_CHECK_ARG(dy && wav && w0 && mean && rstd && dw0 && workspace, "audio_conv1_ln_gelu_bwd: null pointer");
-  OP_CHECK_ARG(rows > 0 && C > 0 && C <= 512 && C % 8 == 0 && stride > 0, "audio_conv1_ln_gelu_bwd: C=%lld (<= 512, multiple of 8), stride=%lld",
+  OP_CHECK_ARG(rows >= 0 && C > 0 && C <= 512 && C % 8 == 0 && stride > 0, "audio_conv1_ln_gelu_bwd: C=%lld (<= 512, multiple of 8), stride=%lld",
                (long long)C, (long long)stride);
   hipStream_t s = (hipStream_t)stream;
+  if (rows == 0) {  // the sum over no rows is zero: non-accumulating outputs are cleared, accumulating ones stay
+    if (!accumulate) {
+      (void)hipMemsetAsync(dw0, 0, (size_t)C * AK * sizeof(bf16_t), s);
+      if (db0) (void)hipMemsetAsync(db0, 0, (size_t)C * sizeof(bf16_t), s);
+      if (dlnw) (void)hipMemsetAsync(dlnw, 0, (size_t)C * sizeof(bf16_t), s);
+      if (dlnb) (void)hipMemsetAsync(dlnb, 0, (size_t)C * sizeof(bf16_t), s);
+    }
+    return OP_OK;
+  }
   const int grid = a_grid(rows);
   const size_t sh = (size_t)4 * C * sizeof(float);
   float* ws = (float*)workspace;

@@ -513,25 +513,34 @@ def audio_conv1_ln_gelu_fwd(wav, stride, w0, b0, lnw, lnb, rows, eps, slack_rows
     """GELU(LN(conv(wav))) of the feature extractor's first block straight from the flat waveform: y [rows + slack_rows, C] (the slack
     rows zero: the next block's strided patch view reads past the last row), mean, rstd [rows]."""
     C = w0.shape[0]
-    assert w0.is_contiguous() and w0.numel() == C * 10 and wav.is_contiguous() and wav.numel() >= stride * (rows - 1) + 10
+    assert w0.is_contiguous() and w0.numel() == C * 10 and wav.is_contiguous() and (rows == 0 or wav.numel() >= stride * (rows - 1) + 10)
     y = torch.empty(rows + slack_rows, C, dtype=torch.bfloat16, device=wav.device)
     if slack_rows:
         y[rows:].zero_()
     mean = torch.empty(rows, dtype=torch.float32, device=wav.device)
     rstd = torch.empty(rows, dtype=torch.float32, device=wav.device)
-    _check(lib().op_audio_conv1_ln_gelu_fwd(ptr(wav), stride, ptr(w0), ptr(b0), ptr(lnw), ptr(lnb), ptr(y), ptr(mean), ptr(rstd), rows, C, eps,
-                                            stream()), "op_audio_conv1_ln_gelu_fwd")
+    # (rows = 0: nothing is written; w0 stands in for the empty tensors' null addresses)
+    _check(lib().op_audio_conv1_ln_gelu_fwd(_ptr_rows(wav, w0), stride, ptr(w0), ptr(b0), ptr(lnw), ptr(lnb), _ptr_rows(y, w0), _ptr_rows(mean, w0),
+                                            _ptr_rows(rstd, w0), rows, C, eps, stream()), "op_audio_conv1_ln_gelu_fwd")
     return y, mean, rstd
 
 
-def audio_conv1_ln_gelu_bwd(dy, wav, stride, w0, b0, lnw, lnb, mean, rstd):
-    """Parameter gradients of audio_conv1_ln_gelu_fwd (bf16): dw0 [C, 10], db0 [C] | None, dlnw [C] | None, dlnb [C] | None."""
+def audio_conv1_ln_gelu_bwd(dy, wav, stride, w0, b0, lnw, lnb, mean, rstd, accumulate=False, out=None):
+    """Parameter gradients of audio_conv1_ln_gelu_fwd (bf16): dw0 [C, 10], db0 [C] | None, dlnw [C] | None, dlnb [C] | None.
+    out = (dw0, db0, dlnw, dlnb): the caller's tensors (None where the parameter is None), overwritten or (accumulate) added to;
+    without `out` they are allocated and accumulate is ignored.  An empty dy (no rows): zeros, or `out` untouched when accumulating."""
     rows, C = dy.shape
-    mk = lambda ref, shape: torch.empty(shape, dtype=torch.bfloat16, device=dy.device) if ref is not None else None  # noqa: E731
-    dw0, db0, dlw, dlb = torch.empty(C, 10, dtype=torch.bfloat16, device=dy.device), mk(b0, C), mk(lnw, C), mk(lnb, C)
+    if out is None:
+        mk = lambda ref, shape: torch.empty(shape, dtype=torch.bfloat16, device=dy.device) if ref is not None else None  # noqa: E731
+        out = torch.empty(C, 10, dtype=torch.bfloat16, device=dy.device), mk(b0, C), mk(lnw, C), mk(lnb, C)
+        accumulate = False
+    dw0, db0, dlw, dlb = out
+    for t, ref, n in ((dw0, w0, C * 10), (db0, b0, C), (dlw, lnw, C), (dlb, lnb, C)):
+        assert (t is None) == (ref is None) and (t is None or (t.dtype == torch.bfloat16 and t.is_contiguous() and t.numel() == n))
     ws = workspace(lib().op_audio_conv1_ln_gelu_bwd_workspace_bytes(C), dy.device, "audio_conv1")
-    _check(lib().op_audio_conv1_ln_gelu_bwd(ptr(dy), ptr(wav), stride, ptr(w0), ptr(b0), ptr(lnw), ptr(lnb), ptr(mean), ptr(rstd), ptr(dw0), ptr(db0),
-                                            ptr(dlw), ptr(dlb), ptr(ws), rows, C, 0, stream()), "op_audio_conv1_ln_gelu_bwd")
+    _check(lib().op_audio_conv1_ln_gelu_bwd(_ptr_rows(dy, ws), _ptr_rows(wav, ws), stride, ptr(w0), ptr(b0), ptr(lnw), ptr(lnb), _ptr_rows(mean, ws),
+                                            _ptr_rows(rstd, ws), ptr(dw0), ptr(db0), ptr(dlw), ptr(dlb), ptr(ws), rows, C, int(accumulate), stream()),
+           "op_audio_conv1_ln_gelu_bwd")
     return dw0, db0, dlw, dlb
 
 

@@ -214,13 +214,14 @@ def fwd_budget(x, w, b, eps, gelu, x_rows=None, e_g0=None):
     return e_y, e_mean, rho * rstd
 
 
-def bwd_budget(kind, dy, x, w, b, mean, rstd, gelu, add=None, x_rows=None, base=None, e_g0=None, out_dtype=None):
+def bwd_budget(kind, dy, x, w, b, mean, rstd, gelu, add=None, x_rows=None, base=None, e_g0=None, out_dtype=None, dw_depth=None):
     """E of dx (the launch's rows), dw, db.  kind ("bwd" | "geglu_bwd") and out_dtype (the kernel's, default bf16) give the route and
-    with it the depth of the dw / db sums."""
+    with it the depth of the dw / db sums; dw_depth replaces that depth for a kernel with a row walk of its own (tests/audio_ref.py)."""
     x = gather_rows(x, x_rows)
     rows, cols = x.shape
     w, b = _affine(w, b, cols, x)
-    D, Dw = depth(cols), wgrad_depth(kind, rows, cols, BF if out_dtype is None else out_dtype)
+    D = depth(cols)
+    Dw = wgrad_depth(kind, rows, cols, BF if out_dtype is None else out_dtype) if dw_depth is None else dw_depth
     r = rstd[:, None]
     xh = (x - mean[:, None]) * r
     e_g = torch.zeros_like(x)

@@ -1007,7 +1007,9 @@ def test_audio_first_block_fused_from_the_waveform(C, bias):
     """(ABI 7) op_audio_conv1_ln_gelu_fwd / _bwd: Conv1d(1 -> C, k = 10, stride 5) -> LayerNorm(C) -> GELU as ONE kernel each way, rows
     computed from their ten waveform samples (adapter/audio.py:254-311, block 0).  Against the fp32 definition (the convolution output
     rounded to bf16 before the statistics, as every bf16 path stores it), forward and all four parameter gradients; and the whole
-    extractor with the fused block against the GEMM + LayerNorm form of rounds 1-4 (ONEPEACE_FUSED_CONV1=0)."""
+    extractor with the fused block against the GEMM + LayerNorm form of rounds 1-4 (ONEPEACE_FUSED_CONV1=0).
+    These are norms over one trip of the row loop (2496 rows); the per-element check against fp64 -- two and three trips, C from 8 to 512,
+    other strides, null arguments, accumulate, rows = 0, silent and non-finite rows, guarded buffers -- is tests/test_audio_fp64_gpu.py."""
     from one_peace_amd import audio_ops
     from one_peace_amd.adapter.audio import ConvFeatureExtractionModel
     hip = hipmod()
