@@ -1259,9 +1259,10 @@ int op_relpos_bias_build_ids(const void* table, const int* bucket, int64_t bucke
   return OP_OK;
 }
 
-// Table gradient from the per-sample bias gradients dbias [B][heads][K][Kpad] fp32 (one slab per sample from op_attn_bwd);
-// dtable [num_rel][heads] fp32 is accumulated into (pre-zero it).  dense_ws: fp32 [heads][Sfull][Sfull] scratch, ZEROED by the
-// caller, Sfull = extent of the bucket table the ids index (the slabs are first folded into it, then scattered onto the table).
+// Stage 1 of the table gradient from the per-sample bias gradients dbias [B][heads][K][Kpad] fp32 (one slab per sample from
+// op_attn_bwd; columns j >= K are not read): the slabs are added into dense_ws, fp32 [heads][Sfull][Sfull] scratch, ZEROED by the
+// caller, Sfull = extent of the bucket table the ids index.  op_relpos_bias_bwd (S = Spad = Sfull) then sums dense_ws onto the
+// table; it OVERWRITES dtable [num_rel][heads] fp32 (include/onepeace_hip.h), so only dense_ws has to be zeroed.
 int op_relpos_bias_fold_ids(const float* dbias, const int* ids, float* dense_ws, int64_t Sfull, int64_t B, int64_t heads, int64_t K,
                             int64_t Kpad, void* stream) {
   OP_CHECK_ARG(dbias && ids && dense_ws && B > 0 && K > 0 && Sfull > 0, "relpos_bias_fold_ids: bad args");
