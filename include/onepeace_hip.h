@@ -523,6 +523,37 @@ int op_sim_topk(const void* Q, int64_t ldq, const void* G, int64_t ldg, int64_t 
 int op_image_resize_normalize(const void* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B,
                               const int* coef, int64_t coef_count, int64_t S, const float* mean, const float* stdev, void* out,
                               int out_dtype, void* workspace, int64_t workspace_bytes, void* stream);
+/* The same entry with the geometry of the training and evaluation transforms.  Additive: op_abi_version() stays 10;
+ * op_image_resize_normalize is this entry with flip = NULL and is unchanged.
+ * RandomHorizontalFlip (data/vision_data/image_classify_dataset.py:59, data/vision_data/nlvr2_dataset.py:37): flip = uint8 [B] on the
+ * DEVICE, non-zero = image i is stored mirrored (column S - 1 - x), in all three output types; NULL = no image is.  The flip comes last, as
+ * in the reference's Compose.  RandomResizedCrop(S, scale, BICUBIC) (data/pretrain_data/image_text_pretrain_dataset.py:46-53) and Resize(S)
+ * + CenterCrop(S) (image_classify_dataset.py:78-84) need no kernel work: PIL's crop(box).resize((S, S)) is the same two passes with the
+ * records of a box-sized image whose first-sample fields are shifted by the box origin, and the centre crop is a window of S records of the
+ * aspect-preserving resize (one-peace_amd/imageprep.py: pack_images(crops = ..., center_crop = ...)); the records of an image may
+ * therefore start anywhere inside it. */
+int op_image_resize_normalize_flip(const void* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B,
+                                   const int* coef, int64_t coef_count, int64_t S, const float* mean, const float* stdev, void* out,
+                                   int out_dtype, void* workspace, int64_t workspace_bytes, const uint8_t* flip, void* stream);
+
+/* ---- batch augmentation: Mixup / CutMix in one pass over the batch (csrc/augment.hip) ------------------------------------------------
+ * Replaces the full-batch torch passes of timm's Mixup as the reference's image-classification collater uses it
+ * (data/vision_data/image_classify_dataset.py:46-51, 117-130).  Additive: op_abi_version() stays 10, no existing entry point changed.
+ * x: [B, CHW] bf16 (in_dtype 0) or f32 (1), dense, CHW = channels * H * W; out: the same shape in out_dtype.  out may be x itself when
+ * the dtypes agree (in place), else the two must not overlap.  kind int32 [B], lam / one_minus_lam fp32 [B] and box int32 [B, 4]
+ * (yl, yh, xl, xh) are DEVICE tables.  Sample i is mixed with its partner j = B - 1 - i of the ORIGINAL batch:
+ *   kind 0  out[i] = x[i]
+ *   kind 1  out[i] = fadd_rn(fmul_rn(x[i], lam[i]), fmul_rn(x[j], one_minus_lam[i])): two rounded fp32 products and one rounded sum, never
+ *           an fma -- torch's x.mul_(lam).add_(x.flip(0).mul_(1 - lam)) bit for bit in fp32
+ *   kind 2  out[i] = x[j] where yl <= y < yh and xl <= x < xh, x[i] elsewhere (an empty box copies; nothing is read through the box)
+ * Any other kind copies.  bf16 inputs are widened exactly; a bf16 output is ONE round-to-nearest-even cast of the fp32 value, as
+ * torch.Tensor.to(bfloat16).  A work item owns the same 8 elements of samples i and j, reads both, then writes both: in place needs no
+ * clone; for odd B the middle sample is its own partner.  One read and one write of the batch, no workspace, no atomics: two runs give
+ * the same bits.  OP_ENOTSUP without a launch unless W % 8 == 0, CHW % 8 == 0 and x, out are 16-byte aligned (the caller falls back);
+ * OP_EINVAL before any launch: unknown dtype, B < 0 or > 131070, H or W < 1, CHW not a multiple of H * W or >= 2^31, null or misaligned tables,
+ * partially overlapping x / out.  B == 0 returns without a launch. */
+int op_mix_images(const void* x, void* out, int in_dtype, int out_dtype, int64_t B, int64_t CHW, int64_t H, int64_t W, const int* kind,
+                  const float* lam, const float* one_minus_lam, const int* box, void* stream);
 
 /* ---- audio pre-processing: channel mean + whole-clip layer norm + crop / tile / pad (csrc/audioprep.hip) -----------------------
  * Replaces the host loop of one_peace/models/one_peace/hub_interface.py:170-193 and data/base_dataset.py:84-102 (audio_postprocess:

@@ -17,6 +17,10 @@
 // PIL runs the vertical pass first for an image more than 100 times taller than wide that shrinks vertically (vfirst = 1; PIL/Image.py,
 // resize).  Such an image is narrow: its first pass filters the source columns into an [S, W, 3] intermediate and its second the
 // intermediate's rows, both with plain byte loads (the `vfirst` branches of the two kernels).
+// The training / evaluation geometry needs no arithmetic of its own (op_image_resize_normalize_flip): RandomResizedCrop
+// (data/pretrain_data/image_text_pretrain_dataset.py:46-53) and Resize + CenterCrop (data/vision_data/image_classify_dataset.py:78-84) are
+// shifted / windowed coefficient records built on the host, and RandomHorizontalFlip (image_classify_dataset.py:59, nlvr2_dataset.py:37) is a
+// per-image flag under which the vertical kernel stores its 4-column group mirrored.
 #include "common.h"
 
 #include <algorithm>
@@ -126,12 +130,14 @@ struct IrNorm { float mean[3], stdev[3]; };
 
 template <int OUT>
 __global__ __launch_bounds__(IR_THREADS) void ir_vertical_kernel(const uint8_t* __restrict__ tmp, const int64_t* __restrict__ desc,
-                                                                 const int* __restrict__ coef, void* __restrict__ out, int S, IrNorm nm) {
+                                                                 const int* __restrict__ coef, void* __restrict__ out, int S, IrNorm nm,
+                                                                 const uint8_t* __restrict__ flip) {
   const int img = blockIdx.y;
   const int64_t* d = desc + (int64_t)img * IR_DESC;
   const int64_t W = d[2], cx_off = d[3], cy_off = d[5], tmp_off = d[7], row0 = d[8], rows = d[9];
   const int kx = (int)d[4], ky = (int)d[6];
   const bool vfirst = d[10] != 0;
+  const bool flipped = flip != nullptr && flip[img] != 0;  // uniform: RandomHorizontalFlip of this image
   const int G = S / 4;
   for (int it = threadIdx.x; it < G * IR_ROWS_V; it += IR_THREADS) {
     const int g = it % G, y = blockIdx.x * IR_ROWS_V + it / G;
@@ -184,8 +190,17 @@ __global__ __launch_bounds__(IR_THREADS) void ir_vertical_kernel(const uint8_t* 
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) u[x][ch] = ir_clip8(acc[x][ch]);
       }
+    // a flipped image writes column S - 1 - x: the 4-column group goes to group G - 1 - g with its columns reversed (same vector stores)
+    const int go = flipped ? G - 1 - g : g;
+    if (flipped) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const int a = u[0][ch], b = u[1][ch];
+        u[0][ch] = u[3][ch], u[1][ch] = u[2][ch], u[2][ch] = b, u[3][ch] = a;
+      }
+    }
     if constexpr (OUT == IR_OUT_U8) {
-      unsigned* q = reinterpret_cast<unsigned*>(reinterpret_cast<uint8_t*>(out) + (((int64_t)img * S + y) * S + g * 4) * 3);
+      unsigned* q = reinterpret_cast<unsigned*>(reinterpret_cast<uint8_t*>(out) + (((int64_t)img * S + y) * S + go * 4) * 3);
       q[0] = (unsigned)u[0][0] | (unsigned)u[0][1] << 8 | (unsigned)u[0][2] << 16 | (unsigned)u[1][0] << 24;
       q[1] = (unsigned)u[1][1] | (unsigned)u[1][2] << 8 | (unsigned)u[2][0] << 16 | (unsigned)u[2][1] << 24;
       q[2] = (unsigned)u[2][2] | (unsigned)u[3][0] << 8 | (unsigned)u[3][1] << 16 | (unsigned)u[3][2] << 24;
@@ -195,7 +210,7 @@ __global__ __launch_bounds__(IR_THREADS) void ir_vertical_kernel(const uint8_t* 
         float v[4];
 #pragma unroll
         for (int x = 0; x < 4; ++x) v[x] = ((float)u[x][ch] / 255.0f - nm.mean[ch]) / nm.stdev[ch];  // torchvision's order, IEEE
-        const int64_t e = (((int64_t)img * 3 + ch) * S + y) * S + g * 4;
+        const int64_t e = (((int64_t)img * 3 + ch) * S + y) * S + go * 4;
         if constexpr (OUT == OP_DT_BF16) {
           bf16x4 r;
 #pragma unroll
@@ -211,9 +226,13 @@ __global__ __launch_bounds__(IR_THREADS) void ir_vertical_kernel(const uint8_t* 
 
 }  // namespace
 
-extern "C" int op_image_resize_normalize(const void* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B,
-                                         const int* coef, int64_t coef_count, int64_t S, const float* mean, const float* stdev,
-                                         void* out, int out_dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+// op_image_resize_normalize plus RandomHorizontalFlip (image_classify_dataset.py:59, nlvr2_dataset.py:37): flip = device uint8 [B], non-zero =
+// this image's columns are stored mirrored; NULL = no image is.  Crops and centre crops need nothing here: they are tables (imageprep.py).
+// Additive: op_abi_version() stays 10.
+extern "C" int op_image_resize_normalize_flip(const void* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B,
+                                              const int* coef, int64_t coef_count, int64_t S, const float* mean, const float* stdev,
+                                              void* out, int out_dtype, void* workspace, int64_t workspace_bytes, const uint8_t* flip,
+                                              void* stream) {
   OP_CHECK_ARG(S >= 16 && S <= IR_MAX_S && S % 16 == 0, "op_image_resize_normalize: S = %lld, need a multiple of 16 in [16, %d]",
                (long long)S, IR_MAX_S);
   OP_CHECK_ARG(B >= 0 && B <= 65535, "op_image_resize_normalize: B = %lld, need 0 ... 65535", (long long)B);
@@ -262,11 +281,18 @@ extern "C" int op_image_resize_normalize(const void* src, int64_t src_bytes, con
   const dim3 grid((unsigned)(S / IR_ROWS_V), (unsigned)B);
   const uint8_t* t = (const uint8_t*)workspace;
   if (out_dtype == OP_DT_BF16)
-    hipLaunchKernelGGL(ir_vertical_kernel<OP_DT_BF16>, grid, dim3(IR_THREADS), 0, st, t, desc, coef, out, (int)S, nm);
+    hipLaunchKernelGGL(ir_vertical_kernel<OP_DT_BF16>, grid, dim3(IR_THREADS), 0, st, t, desc, coef, out, (int)S, nm, flip);
   else if (out_dtype == OP_DT_F32)
-    hipLaunchKernelGGL(ir_vertical_kernel<OP_DT_F32>, grid, dim3(IR_THREADS), 0, st, t, desc, coef, out, (int)S, nm);
+    hipLaunchKernelGGL(ir_vertical_kernel<OP_DT_F32>, grid, dim3(IR_THREADS), 0, st, t, desc, coef, out, (int)S, nm, flip);
   else
-    hipLaunchKernelGGL(ir_vertical_kernel<IR_OUT_U8>, grid, dim3(IR_THREADS), 0, st, t, desc, coef, out, (int)S, nm);
+    hipLaunchKernelGGL(ir_vertical_kernel<IR_OUT_U8>, grid, dim3(IR_THREADS), 0, st, t, desc, coef, out, (int)S, nm, flip);
   OP_LAUNCH_CHECK();
   return OP_OK;
+}
+
+extern "C" int op_image_resize_normalize(const void* src, int64_t src_bytes, const int64_t* desc, const int64_t* desc_host, int64_t B,
+                                         const int* coef, int64_t coef_count, int64_t S, const float* mean, const float* stdev,
+                                         void* out, int out_dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+  return op_image_resize_normalize_flip(src, src_bytes, desc, desc_host, B, coef, coef_count, S, mean, stdev, out, out_dtype, workspace,
+                                        workspace_bytes, nullptr, stream);
 }

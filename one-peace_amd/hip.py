@@ -100,6 +100,8 @@ SIGNATURES = {
     "op_sim_topk_workspace_bytes": (I64, [I64, I64, I64, I64]),
     "op_sim_topk": (c_int, [P, I64, P, I64, I64, I64, I64, I64, P, P, P, I64, I64, P]),
     "op_image_resize_normalize": (c_int, [P, I64, P, P, I64, P, I64, I64, P, P, P, c_int, P, I64, P]),
+    "op_image_resize_normalize_flip": (c_int, [P, I64, P, P, I64, P, I64, I64, P, P, P, c_int, P, I64, P, P]),
+    "op_mix_images": (c_int, [P, P, c_int, c_int, I64, I64, I64, I64, P, P, P, P, P]),
     "op_audio_normalize_pad": (c_int, [P, I64, P, P, I64, I64, I64, P, I64, c_int, P, I64, P]),
     "op_audio_resample": (c_int, [P, I64, P, P, I64, P, I64, P, I64, P]),
     "op_average_precision_workspace_bytes": (I64, [I64, I64]),
@@ -1334,10 +1336,59 @@ def image_resize_normalize(packed, mean=None, std=None, dtype=torch.bfloat16, de
         base = buf.data_ptr()
         m = (c_float * 3)(*mean) if mean is not None else None
         sd = (c_float * 3)(*std) if std is not None else None
-        _check(lib().op_image_resize_normalize(c_void_p(base), packed.src_bytes, c_void_p(base + packed.desc_off),
-                                               packed.desc.ctypes.data_as(c_void_p), B, c_void_p(base + packed.coef_off),
-                                               packed.coef_count, S, m, sd, ptr(out), _IMAGE_OUT[dtype], ptr(ws), ws.numel(), stream()),
-               "op_image_resize_normalize")
+        args = (c_void_p(base), packed.src_bytes, c_void_p(base + packed.desc_off), packed.desc.ctypes.data_as(c_void_p), B,
+                c_void_p(base + packed.coef_off), packed.coef_count, S, m, sd, ptr(out), _IMAGE_OUT[dtype], ptr(ws), ws.numel())
+        if getattr(packed, "flip_off", None) is None:
+            _check(lib().op_image_resize_normalize(*args, stream()), "op_image_resize_normalize")
+        else:  # the per-image flip flags travel in the same buffer (imageprep.pack_images(flips = ...))
+            _check(lib().op_image_resize_normalize_flip(*args, c_void_p(base + packed.flip_off), stream()), "op_image_resize_normalize_flip")
+    return out
+
+
+ENOTSUP = -95  # OP_ENOTSUP (csrc/common.h)
+
+
+def mix_tables(params, B, device):
+    """The (kind int32 [B], lam fp32 [B], one_minus_lam fp32 [B], box int32 [B, 4]) tables of ops.mix_images on `device`, staged as ONE
+    16 x B-byte buffer (one H2D copy) when they come from the host."""
+    import numpy as np
+    kind, lam, oml, box = params
+    if all(torch.is_tensor(t) and t.device == device for t in params):
+        return (kind.to(torch.int32).contiguous(), lam.to(torch.float32).contiguous(), oml.to(torch.float32).contiguous(),
+                box.to(torch.int32).contiguous())
+    host = np.empty((7, B), dtype=np.int32)
+    as_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    host[0] = as_np(kind).astype(np.int32).reshape(B)
+    host[1] = as_np(lam).astype(np.float32).reshape(B).view(np.int32)
+    host[2] = as_np(oml).astype(np.float32).reshape(B).view(np.int32)
+    host[3:] = as_np(box).astype(np.int32).reshape(B, 4).T
+    dev = torch.from_numpy(host).to(device)
+    return dev[0], dev[1].view(torch.float32), dev[2].view(torch.float32), dev[3:].t().contiguous()
+
+
+def mix_images(x, params, out=None):
+    """op_mix_images on x [B, C, H, W] bf16 / fp32 (contiguous, CUDA) with the device tables `params` of mix_tables: Mixup / CutMix of
+    sample i with sample B - 1 - i into `out` (x itself = in place; None = a new tensor of x's dtype).  Returns out, or None when the
+    library answers OP_ENOTSUP (W or C H W not a multiple of 8, unaligned pointers): the caller takes the torch route."""
+    _req(x, "x")
+    out = torch.empty_like(x) if out is None else out
+    _req(out, "out")
+    if x.dim() != 4 or out.shape != x.shape:
+        raise ValueError("mix_images: x and out must be [B, C, H, W] of one shape, got %s and %s" % (tuple(x.shape), tuple(out.shape)))
+    kind, lam, oml, box = params
+    B, C, H, W = x.shape
+    for t, name, dt, n in ((kind, "kind", torch.int32, B), (lam, "lam", torch.float32, B), (oml, "one_minus_lam", torch.float32, B),
+                           (box, "box", torch.int32, 4 * B)):
+        _req(t, name, dt)
+        if t.numel() != n:
+            raise ValueError("mix_images: %s has %d elements, need %d" % (name, t.numel(), n))
+    if B == 0 or C * H * W == 0:
+        return out
+    with torch.cuda.device(x.device):
+        rc = lib().op_mix_images(ptr(x), ptr(out), _dt(x), _dt(out), B, C * H * W, H, W, ptr(kind), ptr(lam), ptr(oml), ptr(box), stream())
+    if rc == ENOTSUP:
+        return None
+    _check(rc, "op_mix_images")
     return out
 
 

@@ -5,7 +5,13 @@ The resize is Pillow's ``Image.resize((S, S), Image.BICUBIC)`` for 8-bit images 
 over the source rows the vertical filter reads, a uint8 intermediate, then the vertical pass, both with 22-bit fixed-point
 weights.  ``bicubic_coeffs`` restates Pillow's ``precompute_coeffs`` + ``normalize_coeffs_8bpc`` so that the device kernel
 (csrc/image.hip, op_image_resize_normalize) reproduces PIL bit for bit; ``pack_images`` stages the images and the tables for one
-host-to-device copy.  ``apply_coeffs`` is the same arithmetic in torch, the CPU reference of the tests only."""
+host-to-device copy.  ``apply_coeffs`` is the same arithmetic in torch, the CPU reference of the tests only.
+
+The training and evaluation geometry rides on the same two passes (no second resize kernel): ``RandomResizedCrop`` (reference
+data/pretrain_data/image_text_pretrain_dataset.py:46-53; boxes from ``random_resized_crop_params``) is the tables of the box with
+shifted column starts, ``Resize(S)`` + ``CenterCrop(S)`` (data/vision_data/image_classify_dataset.py:78-84) a window of the tables of
+the aspect-preserving resize, and ``RandomHorizontalFlip`` (image_classify_dataset.py:59, nlvr2_dataset.py:37) a per-image flag the
+vertical kernel honours when it stores (op_image_resize_normalize_flip).  ``apply_packed`` evaluates a packed batch's tables on the CPU."""
 import math
 
 import numpy as np
@@ -114,14 +120,15 @@ class PackedImages:
 
     Layout of the ONE buffer (pinned on the host, copied to the device with one H2D copy): the images back to back (each at a
     16-byte aligned offset) plus SRC_SLACK readable bytes, then the descriptor table int64 [B, DESC_FIELDS], then the coefficient
-    records int32.  A record is [xmin, taps, 0, 0, w_0 ... w_{k-1}] with k a multiple of 4 (zero-padded), S records per axis and
-    image.  `desc` is the host copy of the table; `workspace_bytes` the size of the uint8 intermediates (rows x S x 3 bytes per image,
-    S x W x 3 for an image whose vertical pass goes first)."""
+    records int32, then (with `flips`) one uint8 flag per image at `flip_off`.  A record is [xmin, taps, 0, 0, w_0 ... w_{k-1}] with k
+    a multiple of 4 (zero-padded), S records per axis and image.  `desc` is the host copy of the table; `workspace_bytes` the size of the
+    uint8 intermediates (rows x S x 3 bytes per image, S x W x 3 for an image whose vertical pass goes first).  With a crop or a centre
+    crop an "image" of the table is the part of the source that was packed (pack_images); `sizes` are those of the whole images."""
 
-    def __init__(self, host, desc, src_bytes, desc_off, coef_off, coef_count, workspace_bytes, size, sizes):
+    def __init__(self, host, desc, src_bytes, desc_off, coef_off, coef_count, workspace_bytes, size, sizes, flip_off=None):
         self.host, self.desc, self.size, self.sizes = host, desc, size, sizes
         self.src_bytes, self.desc_off, self.coef_off, self.coef_count = src_bytes, desc_off, coef_off, coef_count
-        self.workspace_bytes = workspace_bytes
+        self.workspace_bytes, self.flip_off = workspace_bytes, flip_off
 
     def __len__(self):
         return self.desc.shape[0]
@@ -148,21 +155,86 @@ def _record_block(coeffs, size):
     return rec, k
 
 
-def pack_images(images, size, pin=True):
-    """PackedImages of uint8 HWC RGB arrays / tensors (H, W >= 1) for an S x S resize."""
+def check_crops(crops, sizes):
+    """The boxes of `crops` as int tuples (top, left, h, w) -- torchvision's F.resized_crop order -- one per (height, width) of
+    `sizes`; a box outside its image or with h or w < 1 is a ValueError."""
+    crops = [tuple(int(v) for v in c) for c in crops]
+    if len(crops) != len(sizes) or any(len(c) != 4 for c in crops):
+        raise ValueError("crops: need one (top, left, h, w) per image, got %d for %d images" % (len(crops), len(sizes)))
+    for i, ((top, left, h, w), (H, W)) in enumerate(zip(crops, sizes)):
+        if h < 1 or w < 1 or top < 0 or left < 0 or top + h > H or left + w > W:
+            raise ValueError("crops: box %d (top %d, left %d, h %d, w %d) is empty or outside its %d x %d image" % (i, top, left, h, w, H, W))
+    return crops
+
+
+def check_flips(flips, count):
+    flips = [bool(f) for f in (flips.tolist() if hasattr(flips, "tolist") else flips)]
+    if len(flips) != count:
+        raise ValueError("flips: need one flag per image, got %d for %d images" % (len(flips), count))
+    return flips
+
+
+def center_crop_geometry(H, W, size):
+    """(new_h, new_w, top, left) of torchvision's Resize(size) + CenterCrop(size) on an H x W image: the shorter side goes to `size`, the
+    longer to int(size * long / short), and the size x size window starts at int(round((n - size) / 2.0)) of each resized side."""
+    if W <= H:
+        new_w, new_h = size, int(size * H / W)
+    else:
+        new_h, new_w = size, int(size * W / H)
+    return new_h, new_w, int(round((new_h - size) / 2.0)), int(round((new_w - size) / 2.0))
+
+
+def _window(coeffs, first, size):
+    return tuple(c[first:first + size] for c in coeffs)
+
+
+def _geometry(a, size, crop, center_crop):
+    """(part of `a` to pack, column table, row table, vertical_first) of one image.  The tables index the packed part.
+    crop (top, left, h, w): PIL's crop(box).resize((S, S)) is the two passes over the box's rows with the tables of a w x h image, the
+    column starts shifted by `left`; a box whose vertical pass goes first (vertical_first of the BOX) is packed as its own narrow image.
+    center_crop: Resize(S) + CenterCrop(S) is the S-record window of the tables of the H x W -> new_h x new_w resize, over the source
+    rows that window reads; PIL decides the order of the passes from the whole image and the un-windowed target."""
+    H, W = a.shape[:2]
+    if crop is not None:
+        top, left, h, w = crop
+        cx, cy = bicubic_coeffs(w, size), bicubic_coeffs(h, size)
+        if vertical_first(h, w, size):
+            return np.ascontiguousarray(a[top:top + h, left:left + w]), cx, cy, True
+        return a[top:top + h], (cx[0] + np.int32(left), cx[1], cx[2]), cy, False
+    if center_crop:
+        new_h, new_w, oy, ox = center_crop_geometry(H, W, size)
+        cx, cy = _window(bicubic_coeffs(W, new_w), ox, size), _window(bicubic_coeffs(H, new_h), oy, size)
+        if vertical_first(H, W, new_h):
+            return a, cx, cy, True
+        r0, r1 = int(cy[0][0]), int(cy[0][-1] + cy[1][-1])
+        return a[r0:r1], cx, (cy[0] - np.int32(r0), cy[1], cy[2]), False
+    return a, bicubic_coeffs(W, size), bicubic_coeffs(H, size), vertical_first(H, W, size)
+
+
+def pack_images(images, size, pin=True, crops=None, center_crop=False, flips=None):
+    """PackedImages of uint8 HWC RGB arrays / tensors (H, W >= 1) for an S x S resize.  crops: one (top, left, h, w) per image, the
+    resize of that box (torchvision's resized_crop); center_crop: torchvision's Resize(S) + CenterCrop(S), exclusive with crops;
+    flips: one bool per image, staged behind the tables for the device (the flip itself is the kernel's)."""
     check_size(size)
     arrs = [as_rgb_array(im) for im in images]
     B = len(arrs)
+    if crops is not None and center_crop:
+        raise ValueError("pack_images: crops and center_crop are mutually exclusive")
+    if crops is not None:
+        crops = check_crops(crops, [a.shape[:2] for a in arrs])
+    if flips is not None:
+        flips = check_flips(flips, B)
+    sizes = [(int(a.shape[1]), int(a.shape[0])) for a in arrs]  # (width, height), as PIL's image.size
     desc = np.zeros((B, DESC_FIELDS), dtype=np.int64)
     blocks, src_off, coef_ints, tmp_off = [], 0, 0, 0
-    for i, a in enumerate(arrs):
+    for i in range(B):
+        a, cx, cy, vfirst = _geometry(arrs[i], size, None if crops is None else crops[i], center_crop)
+        arrs[i] = a
         H, W = a.shape[:2]
-        cx, cy = bicubic_coeffs(W, size), bicubic_coeffs(H, size)
         if max(np.abs(cx[2]).max(), np.abs(cy[2]).max()) >= 1 << 23:  # the kernel multiplies on the 24-bit multiplier
             raise ValueError("pack_images: a filter weight of %d x %d -> %d does not fit 24 bits" % (H, W, size))
         rx, kx = _record_block(cx, size)
         ry, ky = _record_block(cy, size)
-        vfirst = vertical_first(H, W, size)
         if vfirst:  # intermediate: the S rows of the vertical pass over all W columns
             row0, rows, tmp_bytes = 0, size, size * W * 3
         else:       # intermediate: the source rows the vertical filter reads, each resized to S columns
@@ -178,6 +250,10 @@ def pack_images(images, size, pin=True):
     desc_off = src_bytes
     coef_off = _align(desc_off + desc.nbytes)
     total = coef_off + coef_ints * 4
+    flip_off = None
+    if flips is not None:
+        flip_off = _align(total)
+        total = flip_off + _align(B)
     host = torch.empty(total, dtype=torch.uint8, pin_memory=pin)
     buf = host.numpy()
     for i, a in enumerate(arrs):
@@ -186,7 +262,68 @@ def pack_images(images, size, pin=True):
         buf[o + a.size:_align(o + a.size)] = 0  # alignment gaps and the slack are read (under zero weights): keep them defined
     buf[src_off:src_bytes] = 0
     buf[desc_off:desc_off + desc.nbytes] = desc.view(np.uint8).reshape(-1)
+    buf[desc_off + desc.nbytes:coef_off] = 0
     if blocks:
-        buf[coef_off:] = np.concatenate(blocks).view(np.uint8)
-    sizes = [(int(a.shape[1]), int(a.shape[0])) for a in arrs]  # (width, height), as PIL's image.size
-    return PackedImages(host, desc, src_bytes, desc_off, coef_off, coef_ints, tmp_off, size, sizes)
+        buf[coef_off:coef_off + coef_ints * 4] = np.concatenate(blocks).view(np.uint8)
+    if flips is not None:
+        buf[coef_off + coef_ints * 4:] = 0
+        buf[flip_off:flip_off + B] = np.asarray(flips, dtype=np.uint8)
+    return PackedImages(host, desc, src_bytes, desc_off, coef_off, coef_ints, tmp_off, size, sizes, flip_off)
+
+
+def apply_packed(packed):
+    """uint8 [B, S, S, 3]: the tables of a PackedImages batch evaluated on its packed pixels with `_pass`, in the order of the two
+    kernels (horizontal pass over rows row0 ... row0 + rows, then the vertical pass; the other order for vfirst), flipped where the
+    staged flag says so.  The CPU restatement of op_image_resize_normalize_flip that the tests pin to PIL."""
+    S, buf = packed.size, packed.host.numpy()
+    coef = buf[packed.coef_off:packed.coef_off + packed.coef_count * 4].view(np.int32)
+    out = torch.empty(len(packed), S, S, 3, dtype=torch.uint8)
+    for i, (src_off, H, W, cx_off, kx, cy_off, ky, _, row0, rows, vfirst) in enumerate(packed.desc.tolist()):
+        img = torch.from_numpy(buf[src_off:src_off + H * W * 3].reshape(H, W, 3).astype(np.int64))
+        rx = coef[cx_off:cx_off + S * (4 + kx)].reshape(S, 4 + kx)
+        ry = coef[cy_off:cy_off + S * (4 + ky)].reshape(S, 4 + ky)
+        cx, cy = (rx[:, 0], rx[:, 1], rx[:, 4:]), (ry[:, 0], ry[:, 1], ry[:, 4:])
+        if vfirst:
+            res = _pass(_pass(img, cy, 0), cx, 1)
+        else:
+            res = _pass(_pass(img[row0:row0 + rows], cx, 1), (cy[0] - row0, cy[1], cy[2]), 0)
+        if packed.flip_off is not None and buf[packed.flip_off + i]:
+            res = res.flip(1)
+        out[i] = res.to(torch.uint8)
+    return out
+
+
+def random_resized_crop_params(height, width, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), generator=None):
+    """(top, left, h, w) of torchvision's RandomResizedCrop.get_params for a height x width image, restated with torch's RNG
+    (`generator`): up to 10 tries of area * U(scale), exp(U(log ratio)), w = int(round(sqrt(a r))), h = int(round(sqrt(a / r))), the
+    first with 0 < w <= width and 0 < h <= height placed at randint(0, height - h + 1), randint(0, width - w + 1); else the central
+    crop whose aspect is clamped into `ratio`.  torchvision is not a dependency of this project: the ALGORITHM and the pixel path of
+    the boxes are checked by the tests, equality of the random stream with torchvision's is NOT checked."""
+    if height < 1 or width < 1:
+        raise ValueError("random_resized_crop_params: need height, width >= 1, got %d x %d" % (height, width))
+    area = height * width
+    log_ratio = (math.log(ratio[0]), math.log(ratio[1]))
+
+    def uniform(lo, hi):
+        return float(torch.empty(1).uniform_(lo, hi, generator=generator))
+
+    def randint(n):
+        return int(torch.randint(0, n, (1,), generator=generator))
+
+    for _ in range(10):
+        target_area = area * uniform(scale[0], scale[1])
+        aspect = math.exp(uniform(log_ratio[0], log_ratio[1]))
+        w = int(round(math.sqrt(target_area * aspect)))
+        h = int(round(math.sqrt(target_area / aspect)))
+        if 0 < w <= width and 0 < h <= height:
+            return randint(height - h + 1), randint(width - w + 1), h, w
+    in_ratio = float(width) / float(height)
+    if in_ratio < min(ratio):
+        w = width
+        h = int(round(w / min(ratio)))
+    elif in_ratio > max(ratio):
+        h = height
+        w = int(round(h * max(ratio)))
+    else:
+        w, h = width, height
+    return (height - h) // 2, (width - w) // 2, h, w

@@ -127,8 +127,10 @@ class OnePeaceHubInterface:
         tensors (a uint8 [B, H, W, 3] batch works too; arrays never need PIL on a device).  On a device the resize and the
         normalisation run in op_image_resize_normalize (bit-identical to PIL + torchvision); on the CPU PIL does the resize.
         A floating-point tensor is taken as already pre-processed and only moved and cast, as before.
-        Out of scope: JPEG / PNG decoding stays in PIL on the host; BPE for process_text, training-time augmentation
-        (RandomResizedCrop, RandAugment) are not provided."""
+        The training transforms (RandomResizedCrop, Resize + CenterCrop, RandomHorizontalFlip) and Mixup / CutMix are
+        augment.TrainImageTransform and augment.Mixup, on the same kernels.
+        Out of scope: JPEG / PNG decoding stays in PIL on the host; BPE for process_text, RandAugment, RandomDistortion / ColorJitter,
+        GaussianBlur and RandomErasing are not provided."""
         from .. import ops
         if torch.is_tensor(image_list) or isinstance(image_list, np.ndarray):
             batch = torch.as_tensor(image_list)

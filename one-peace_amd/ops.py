@@ -656,31 +656,122 @@ def _is_pil(im):
     return type(im).__module__.startswith("PIL.") and hasattr(im, "convert")
 
 
-def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, device="cpu"):
+def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, device="cpu", crops=None, center_crop=False, flips=None):
     """[B, 3, size, size] in `dtype` on `device` from decoded RGB images (uint8 [H, W, 3] arrays / tensors or PIL images of any
     size): PIL's Image.resize((size, size), BICUBIC), ToTensor and Normalize (CLIP mean / std by default) in torchvision's fp32
     order, then the cast -- the reference's transform, bit for bit.  On a CUDA device this is op_image_resize_normalize
     (hip.image_resize_normalize: one H2D copy of the uint8 pixels, resize and normalisation on the GPU; PIL is not needed for
-    arrays); on the CPU it is PIL itself and the same torch arithmetic (the reference's own path)."""
+    arrays); on the CPU it is PIL itself and the same torch arithmetic (the reference's own path).
+
+    The geometry of the training / evaluation transforms rides on the same pass.  crops: one (top, left, h, w) per image
+    (torchvision's F.resized_crop order; imageprep.random_resized_crop_params draws RandomResizedCrop's), the box is resized instead of
+    the image.  center_crop=True: torchvision's Resize(size) + CenterCrop(size) (shorter side to size, the longer to
+    int(size * long / short), window at int(round((n - size) / 2.0))); exclusive with crops.  flips: one bool per image,
+    RandomHorizontalFlip, applied last as in the reference's Compose.  A box outside its image or with h or w < 1 is a ValueError
+    before anything is copied."""
     import numpy as np
 
     from . import imageprep
     mean = imageprep.CLIP_MEAN if mean is None else tuple(mean)
     std = imageprep.CLIP_STD if std is None else tuple(std)
     imageprep.check_size(size)
+    if crops is not None and center_crop:
+        raise ValueError("preprocess_images: crops and center_crop are mutually exclusive")
+    images = list(images)
+    if crops is not None:
+        hw = [(im.size[1], im.size[0]) if _is_pil(im) else tuple(im.shape[:2]) for im in images]
+        crops = imageprep.check_crops(crops, hw)
+    if flips is not None:
+        flips = imageprep.check_flips(flips, len(images))
     dev = torch.device(device)
     if dev.type == "cuda":
         arrs = [np.asarray(im.convert("RGB")) if _is_pil(im) else im for im in images]
-        packed = imageprep.pack_images(arrs, size)
+        packed = imageprep.pack_images(arrs, size, crops=crops, center_crop=center_crop, flips=flips)
         kdt = dtype if dtype in (torch.bfloat16, torch.float32) else torch.float32
         return hip.image_resize_normalize(packed, mean, std, kdt, dev).to(dtype)
     from PIL import Image
     out = []
-    for im in images:
+    for i, im in enumerate(images):
         im = im.convert("RGB") if _is_pil(im) else Image.fromarray(imageprep.as_rgb_array(im))
-        u8 = torch.from_numpy(np.array(im.resize((size, size), Image.BICUBIC), dtype=np.uint8))
+        if crops is not None:
+            top, left, h, w = crops[i]
+            im = im.crop((left, top, left + w, top + h)).resize((size, size), Image.BICUBIC)
+        elif center_crop:
+            new_h, new_w, top, left = imageprep.center_crop_geometry(im.size[1], im.size[0], size)
+            im = im.resize((new_w, new_h), Image.BICUBIC).crop((left, top, left + size, top + size))
+        else:
+            im = im.resize((size, size), Image.BICUBIC)
+        if flips is not None and flips[i]:
+            im = im.transpose(Image.FLIP_LEFT_RIGHT)
+        u8 = torch.from_numpy(np.array(im, dtype=np.uint8))
         out.append(imageprep.to_tensor_normalize(u8, mean, std))
     return torch.stack(out).to(device=dev, dtype=dtype) if out else torch.empty(0, 3, size, size, dtype=dtype, device=dev)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# Mixup / CutMix: timm's Mixup as data/vision_data/image_classify_dataset.py:46-51, 117-130 uses it (augment.Mixup draws the tables)
+# --------------------------------------------------------------------------------------------------------------
+def _mix_images_torch(x, kind, lam, oml, box, out_dtype):
+    """The reference's statement per sample, in fp32 on x's device: x.mul(lam).add(x.flip(0).mul(1 - lam)) where kind is 1, the partner's
+    pixels inside the box where it is 2, x elsewhere; then ONE cast to out_dtype."""
+    B, _, H, W = x.shape
+    xf = x.float()
+    part = xf.flip(0)
+    v = lambda t: t.to(xf.device).view(B, 1, 1, 1)
+    mixed = xf.mul(v(lam)).add(part.mul(v(oml)))
+    ys = torch.arange(H, device=xf.device).view(1, 1, H, 1)
+    xs = torch.arange(W, device=xf.device).view(1, 1, 1, W)
+    b = box.to(xf.device).view(B, 4, 1, 1, 1)
+    inside = (ys >= b[:, 0]) & (ys < b[:, 1]) & (xs >= b[:, 2]) & (xs < b[:, 3])
+    k = v(kind)
+    return torch.where(k == 1, mixed, torch.where((k == 2) & inside, part, xf)).to(out_dtype)
+
+
+def mix_images(x, params, out_dtype=None, inplace=False):
+    """Mixup / CutMix of an image batch x [B, C, H, W] with the per-sample tables params = (kind int32 [B], lam fp32 [B],
+    one_minus_lam fp32 [B], box int32 [B, 4] as yl, yh, xl, xh) of augment.Mixup.params: sample i is mixed with sample B - 1 - i of
+    the ORIGINAL batch -- kind 0 copy, 1 x[i] * lam + x[j] * one_minus_lam (two rounded fp32 products, one rounded sum: torch's
+    x.mul_(lam).add_(x.flip(0).mul_(1 - lam)) bit for bit), 2 the partner's pixels inside the box.  CUDA fp32 / bf16 batches run
+    op_mix_images (one read and one write of the batch, in place without a clone); anything else, and shapes the kernel does not
+    support (W or C H W not a multiple of 8), the torch statement (the reference's own path).  bf16 inputs are widened, mixed in
+    fp32 and rounded ONCE (torch's bf16 arithmetic would round three times).  out_dtype: float32 / bfloat16 (default: x's);
+    inplace=True (out_dtype = x's dtype) writes into x and returns it."""
+    if x.dim() != 4:
+        raise ValueError("mix_images: x must be [B, C, H, W], got %s" % (tuple(x.shape),))
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if inplace and out_dtype != x.dtype:
+        raise ValueError("mix_images: in place needs out_dtype = x's dtype, got %s for %s" % (out_dtype, x.dtype))
+    B = x.shape[0]
+    as_t = lambda t, dt: (t if torch.is_tensor(t) else torch.as_tensor(t)).to(dt).reshape(-1)
+    kind, lam, oml, box = params
+    kind, lam, oml, box = as_t(kind, torch.int32), as_t(lam, torch.float32), as_t(oml, torch.float32), as_t(box, torch.int32)
+    if not (kind.numel() == lam.numel() == oml.numel() == B and box.numel() == 4 * B):
+        raise ValueError("mix_images: tables must have B = %d rows (box [B, 4])" % B)
+    dts = (torch.float32, torch.bfloat16)
+    if x.is_cuda and x.dtype in dts and out_dtype in dts and B > 0:
+        xc = x if x.is_contiguous() else x.contiguous()
+        out = xc if (inplace and xc is x) else torch.empty(xc.shape, dtype=out_dtype, device=x.device)
+        got = hip.mix_images(xc, hip.mix_tables((kind, lam, oml, box.view(B, 4)), B, x.device), out)
+        if got is not None:
+            return x.copy_(got) if (inplace and got is not x) else got
+    res = _mix_images_torch(x, kind, lam, oml, box.view(B, 4), out_dtype)
+    return x.copy_(res) if inplace else res
+
+
+def mix_targets(target, num_classes, lam=1.0, smoothing=0.0):
+    """fp32 [B, num_classes]: timm's mixup_target in torch ops on the labels' device -- off = smoothing / C, on = 1 - smoothing + off,
+    y1 = full(off).scatter_(1, t, on), y2 the same of t.flip(0), y1 * lam + y2 * (1 - lam).  lam: a Python float (batch mode) or one
+    value per sample ([B] tensor / array, elem and pair modes).  The soft targets ops.classify_loss consumes (ROW_LOSS_SOFT)."""
+    off = smoothing / num_classes
+    on = 1.0 - smoothing + off
+    t = target.long().view(-1, 1)
+
+    def one_hot(idx):
+        return torch.full((idx.shape[0], num_classes), off, dtype=torch.float32, device=idx.device).scatter_(1, idx, on)
+
+    if not isinstance(lam, (int, float)):
+        lam = (lam if torch.is_tensor(lam) else torch.as_tensor(lam)).to(device=t.device, dtype=torch.float32).view(-1, 1)
+    return one_hot(t) * lam + one_hot(t.flip(0)) * (1.0 - lam)
 
 
 # --------------------------------------------------------------------------------------------------------------
