@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 /* ---- library ------------------------------------------------------------------------------------------------ */
-int op_abi_version(void); /* 2: per-call `tune` words replaced the process-wide knob setters; 3: op_gemm_nt_grouped, op_ln_geglu_fwd, ldd / ldh of op_ln_geglu_bwd, `out` of op_attn_bwd; 4: op_gemm_tn_grouped; 5: op_probe_mfma_rate, op_rows_gather / op_rows_merge, 16-byte rule of op_gemm_tn_grouped's C; 6: the op_probe_* entry points left for libonepeace_probe.so (include/onepeace_probe.h), op_gemm_nt_grouped answers OP_ENOTSUP for the GeGLU epilogue, op_gemm_tn_grouped_plan takes the workgroup count and tune word; 7: W / ldw / rowdot of op_gemm_tn_grouped, g0 of op_resid_bwd, op_gamma_grad_finish, op_gemm_nt_batched, op_audio_conv1_ln_gelu_fwd / _bwd; 8: the layer-scale gradient without a division -- rscale of op_gemm_tn_grouped, op_transpose_scaled + the scale member of the op_transpose_batched descriptor, op_resid_bwd leaves gamma out of dbranch when g0 is asked for, op_gamma_grad_finish lost its gamma argument; rowdot is a [N / 128][M] matrix of partial sums written once each (no atomics); 9: row tables -- a residual branch that runs on the samples stochastic depth keeps reads and writes the FULL activation matrix through op_rows_map's table instead of through packed copies: x_rows of op_layernorm_fwd / op_layernorm_bwd, dout_rows of op_resid_bwd, resid_rows / resid_rows_total of op_gemm_nt and op_gemm_nt_grouped, op_rows_merge without `upd` copies the dropped samples' rows only; op_prof_reserve; 10: run-to-run identical gradients -- op_relpos_bias_bwd sums the table gradient in a fixed order from pair lists instead of scattering with atomics, op_relpos_bias_bwd_ids became op_relpos_bias_fold_ids, the separate dBias kernel of op_attn_bwd adds into one slab per batch chunk; (still 10, additive) op_live_ktiles + op_gemm_tn_grouped_lists: the weight gradients skip the K-tiles of samples stochastic depth dropped; (still 10, additive) op_live_mwindows + op_gemm_nt_grouped_windows: the input gradients skip their row blocks; (still 10, additive) op_live_mwindows_fwd + op_gemm_nt_grouped_windows_fwd: the forward GEMMs of a residual branch skip them too */
+int op_abi_version(void); /* 2: per-call `tune` words replaced the process-wide knob setters; 3: op_gemm_nt_grouped, op_ln_geglu_fwd, ldd / ldh of op_ln_geglu_bwd, `out` of op_attn_bwd; 4: op_gemm_tn_grouped; 5: op_probe_mfma_rate, op_rows_gather / op_rows_merge, 16-byte rule of op_gemm_tn_grouped's C; 6: the op_probe_* entry points left for libonepeace_probe.so (include/onepeace_probe.h), op_gemm_nt_grouped answers OP_ENOTSUP for the GeGLU epilogue, op_gemm_tn_grouped_plan takes the workgroup count and tune word; 7: W / ldw / rowdot of op_gemm_tn_grouped, g0 of op_resid_bwd, op_gamma_grad_finish, op_gemm_nt_batched, op_audio_conv1_ln_gelu_fwd / _bwd; 8: the layer-scale gradient without a division -- rscale of op_gemm_tn_grouped, op_transpose_scaled + the scale member of the op_transpose_batched descriptor, op_resid_bwd leaves gamma out of dbranch when g0 is asked for, op_gamma_grad_finish lost its gamma argument; rowdot is a [N / 128][M] matrix of partial sums written once each (no atomics); 9: row tables -- a residual branch that runs on the samples stochastic depth keeps reads and writes the FULL activation matrix through op_rows_map's table instead of through packed copies: x_rows of op_layernorm_fwd / op_layernorm_bwd, dout_rows of op_resid_bwd, resid_rows / resid_rows_total of op_gemm_nt and op_gemm_nt_grouped, op_rows_merge without `upd` copies the dropped samples' rows only; op_prof_reserve; 10: run-to-run identical gradients -- op_relpos_bias_bwd sums the table gradient in a fixed order from pair lists instead of scattering with atomics, op_relpos_bias_bwd_ids became op_relpos_bias_fold_ids, the separate dBias kernel of op_attn_bwd adds into one slab per batch chunk; (still 10, additive) op_live_ktiles + op_gemm_tn_grouped_lists: the weight gradients skip the K-tiles of samples stochastic depth dropped; (still 10, additive) op_live_mwindows + op_gemm_nt_grouped_windows: the input gradients skip their row blocks; (still 10, additive) op_live_mwindows_fwd + op_gemm_nt_grouped_windows_fwd: the forward GEMMs of a residual branch skip them too; (still 10, additive) op_ln_geglu_fwd_skip / op_ln_geglu_bwd_skip / op_layernorm_bwd_skip / op_resid_bwd_skip: the row kernels do not read the rows of dropped samples */
 const char* op_last_error(void);
 
 /* Live per-kernel-family timing with HIP events recorded on the launch stream (used by bench.py's `roofline`).
@@ -55,6 +55,13 @@ int op_layernorm_bwd(const void* dy, const void* x, const void* w, const void* b
                      int act_gelu, int accumulate, int dtype, const int* x_rows, void* stream);
 /* (ABI 9) x_rows as in op_layernorm_fwd: x, add AND dx are then rows x_rows[r] of larger matrices (dy, mean, rstd by r); rows with an
  * entry < 0 are not stored.  With dx == add (in place) the rows no entry names keep `add`: the gradient of the skip connection. */
+/* (additive, ABI 10) op_layernorm_bwd (bf16, no GELU, no row table) without the rows of the samples stochastic depth dropped (ps /
+ * rows_per_sample as in op_ln_geglu_fwd_skip): nothing of dy, x, mean, rstd is read for a row with ps == 0; dx gets +0 there, or the
+ * bits of the `add` row (dx may be add); dw / db get no contribution.  Other rows, dw and db: op_layernorm_bwd's bits.  ps null:
+ * op_layernorm_bwd.  rows < 2^31. */
+int op_layernorm_bwd_skip(const void* dy, const void* x, const void* w, const float* mean, const float* rstd, const void* add, void* dx,
+                          void* dw, void* db, void* workspace, int64_t rows, int64_t cols, int accumulate, const float* ps,
+                          int64_t rows_per_sample, void* stream);
 
 /* ---- bf16 MFMA GEMM  C[M,N] = A[M,K] . W[N,K]^T  with fused epilogues ---------------------------------------------
  * Replaces: q/k/v/out projections (multihead_attention.py:63-66,103-105,124; up to three weight segments of n_seg rows
@@ -351,6 +358,11 @@ int64_t op_resid_bwd_workspace_bytes(int64_t N);
 int op_resid_bwd(const void* dout, const void* y, const void* gamma, const float* rowscale, int64_t rows_per_sample,
                  void* dbranch, void* dgamma, void* dbias, float* g0, void* workspace, int64_t M, int64_t N, int accumulate,
                  const int* dout_rows, void* stream); /* (ABI 9) dout_rows: nullable DEVICE int32 [M]: row m of dout is row dout_rows[m] of a larger matrix (< 0: zeros); y / dbranch by m */
+/* (additive, ABI 10) op_resid_bwd that reads the multiplier of a row first: where rowscale[m / rows_per_sample] == 0 nothing of
+ * dout / y is loaded, dbranch gets +0 and the column sums no contribution.  Other rows and the sums: op_resid_bwd's bits. */
+int op_resid_bwd_skip(const void* dout, const void* y, const void* gamma, const float* rowscale, int64_t rows_per_sample,
+                      void* dbranch, void* dgamma, void* dbias, float* g0, void* workspace, int64_t M, int64_t N, int accumulate,
+                      const int* dout_rows, void* stream);
 /* (ABI 7; 8: no gamma argument, no division, partial slots instead of atomics) Layer-scale gradient of a residual branch
  * out = resid + rowscale * gamma * (x W^T + b)  WITHOUT the branch output:
  *   dgamma[n] (+)= sum_{s < slots} rowdot[s][n] + sum_i b_i[n] * g0_i[n]
@@ -374,6 +386,16 @@ int op_ln_geglu_bwd(const void* dy, const void* h0, const void* h1, const void* 
  * HBM-bound pass costs in total. */
 int op_ln_geglu_fwd(const void* h0, const void* h1, int64_t ldh, const void* w, const void* b, void* y, float* mean, float* rstd,
                     int64_t rows, int64_t cols, float eps, void* stream);
+/* (additive, ABI 10) The same pair without the rows of the samples stochastic depth dropped: row r belongs to sample
+ * r / rows_per_sample (>= 1; 1 serves a per-row vector), ps: DEVICE fp32, one multiplier per sample.  Where ps[sample] == 0 nothing of
+ * the row is read (h0 | h1, dy, mean and rstd may hold anything there, NaN included).  Forward: y gets +0 there; mean / rstd of the row
+ * are not written.  Backward: dh0 | dh1 get +0 and dw / db no contribution -- what op_ln_geglu_bwd gives for an exact-zero dy row.
+ * All other rows, and dw / db, have the plain entries' bits.  ps null: the plain entries.  rows < 2^31. */
+int op_ln_geglu_fwd_skip(const void* h0, const void* h1, int64_t ldh, const void* w, const void* b, void* y, float* mean, float* rstd,
+                         int64_t rows, int64_t cols, float eps, const float* ps, int64_t rows_per_sample, void* stream);
+int op_ln_geglu_bwd_skip(const void* dy, const void* h0, const void* h1, const void* w, const float* mean, const float* rstd,
+                         void* dh0, void* dh1, int64_t ldd, int64_t ldh, void* dw, void* db, void* workspace, int64_t rows,
+                         int64_t cols, int accumulate, const float* ps, int64_t rows_per_sample, void* stream);
 /* out[n] = (accumulate ? out[n] : 0) + mul[n] * sum_m rowscale[m/rps] * x[m][n] * (y ? y[m][n] : 1); y/rowscale/mul NULL ok */
 int op_colsum(const void* x, const void* y, const float* rowscale, int64_t rows_per_sample, const void* mul, void* out,
               void* workspace, int64_t M, int64_t N, int accumulate, int out_dtype, void* stream);

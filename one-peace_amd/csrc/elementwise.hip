@@ -172,7 +172,11 @@ __global__ __launch_bounds__(256) void gamma_grad_finish_kernel(const float* __r
 //   part[0][p][n] = sum_rows rs * dout * y        (-> dgamma)
 //   part[1][p][n] = sum_rows rs * dout            (-> dbias of the branch's last Linear, times gamma in the fold)
 // grid = (ceil(N / 512), parts); block 256 = 4 waves x 64 lanes x 8 columns; two rows in flight per wave.
+// SKIP (rs given): the multiplier of a row is read a trip BEFORE the row; where it is 0 nothing of dout / y is loaded, dbranch gets +0 and
+// the partial sums get nothing -- the dense kernel multiplies that row by the exact zero.  (A wave walks one row and the loop holds
+// no barrier.)
 // ------------------------------------------------------------------------------------------------------------
+template <bool SKIP>
 __global__ __launch_bounds__(256) void resid_bwd_kernel(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ y,
                                                         const bf16_t* __restrict__ gamma, const float* __restrict__ rowscale,
                                                         int rps, bf16_t* __restrict__ dbranch, float* __restrict__ part,
@@ -189,6 +193,11 @@ __global__ __launch_bounds__(256) void resid_bwd_kernel(const bf16_t* __restrict
     const int64_t mfirst = (int64_t)blockIdx.y * 4 + wid;
     // (table entries of the NEXT trip are requested before this trip's rows are used: in one trip, entry -> row is an L2 latency per trip)
     int64_t e0 = (rows && mfirst < M) ? rows[mfirst] : mfirst, e1 = (rows && mfirst + step < M) ? rows[mfirst + step] : mfirst + step;
+    float n0 = 1.f, n1 = 1.f;  // SKIP: the multipliers of the next trip's two rows, requested a trip ahead like the table entries
+    if constexpr (SKIP) {
+      if (mfirst < M) n0 = rowscale[mfirst / rps];
+      if (mfirst + step < M) n1 = rowscale[(mfirst + step) / rps];
+    }
     for (int64_t m = mfirst; m < M; m += 2 * step) {
       const int64_t m2 = m + step;
       const bool two = m2 < M;
@@ -202,9 +211,15 @@ __global__ __launch_bounds__(256) void resid_bwd_kernel(const bf16_t* __restrict
         e1 = mn + step;
       }
       const bf16x8 zero8 = {(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
-      bf16x8 d0 = s0 >= 0 ? Vec8<bf16_t>::ldraw(dout + s0 * N + c) : zero8, d1, y0, y1;
-      if (y) y0 = Vec8<bf16_t>::ldraw(y + m * N + c);
-      if (two) {
+      const float sc0 = n0, sc1 = n1;
+      if constexpr (SKIP) {
+        if (mn < M) n0 = rowscale[mn / rps];
+        if (mn + step < M) n1 = rowscale[(mn + step) / rps];
+      }
+      const bool live0 = !SKIP || sc0 != 0.f, live1 = two && (!SKIP || sc1 != 0.f);
+      bf16x8 d0 = (s0 >= 0 && live0) ? Vec8<bf16_t>::ldraw(dout + s0 * N + c) : zero8, d1, y0, y1;
+      if (y && live0) y0 = Vec8<bf16_t>::ldraw(y + m * N + c);
+      if (live1) {
         d1 = s1 >= 0 ? Vec8<bf16_t>::ldraw(dout + s1 * N + c) : zero8;
         if (y) y1 = Vec8<bf16_t>::ldraw(y + m2 * N + c);
       }
@@ -212,9 +227,13 @@ __global__ __launch_bounds__(256) void resid_bwd_kernel(const bf16_t* __restrict
       for (int h = 0; h < 2; ++h) {
         if (h == 1 && !two) break;
         const int64_t mm = h == 0 ? m : m2;
+        if (SKIP && !(h == 0 ? live0 : live1)) {
+          *reinterpret_cast<bf16x8*>(dbranch + mm * N + c) = zero8;
+          continue;
+        }
         float d[8], o[8];
         Vec8<bf16_t>::cvt(h == 0 ? d0 : d1, d);
-        const float sc = rowscale ? rowscale[mm / rps] : 1.f;
+        const float sc = SKIP ? (h == 0 ? sc0 : sc1) : (rowscale ? rowscale[mm / rps] : 1.f);
         if (y) {
           float yv[8];
           Vec8<bf16_t>::cvt(h == 0 ? y0 : y1, yv);
@@ -981,9 +1000,9 @@ int64_t op_resid_bwd_workspace_bytes(int64_t N) { return 2 * (int64_t)CS_MAX_PAR
 // y = the branch's last Linear output incl. its bias):
 //   dbranch = rowscale * gamma * dout;  dgamma (+)= sum_m rowscale * dout * y;  dbias (+)= sum_m dbranch
 // gamma, rowscale, y/dgamma, dbias nullable; dgamma/dbias are bf16 [N]; accumulate: add into them instead of overwriting.
-int op_resid_bwd(const void* dout, const void* y, const void* gamma, const float* rowscale, int64_t rows_per_sample,
-                 void* dbranch, void* dgamma, void* dbias, float* g0, void* workspace, int64_t M, int64_t N, int accumulate,
-                 const int* dout_rows, void* stream) {
+static int resid_bwd_impl(const void* dout, const void* y, const void* gamma, const float* rowscale, int64_t rows_per_sample,
+                          void* dbranch, void* dgamma, void* dbias, float* g0, void* workspace, int64_t M, int64_t N, int accumulate,
+                          const int* dout_rows, int skip_zero_rows, void* stream) {
   OP_CHECK_ARG(dout && dbranch, "resid_bwd: null pointer");
   OP_CHECK_ARG(N > 0 && N % 8 == 0, "resid_bwd: N must be a multiple of 8");
   OP_CHECK_ARG(!dgamma || y, "resid_bwd: dgamma needs y");
@@ -1004,9 +1023,12 @@ int op_resid_bwd(const void* dout, const void* y, const void* gamma, const float
   float* ws = (dgamma || dbias || g0) ? (float*)workspace : nullptr;
   // (ABI 8) g0 wanted = the layer-scale gradient comes from the weight gradient: dbranch stays WITHOUT gamma (the weight-gradient and
   // input-gradient GEMMs carry it: op_gemm_tn_grouped's rscale, op_transpose_scaled), dbias still gets it in the fold
-  hipLaunchKernelGGL(resid_bwd_kernel, dim3(ceil_div(N, 512), parts), dim3(256), 0, s, (const bf16_t*)dout,
-                     (const bf16_t*)(dgamma ? y : nullptr), (const bf16_t*)(g0 ? nullptr : gamma), rowscale,
-                     (int)(rows_per_sample > 0 ? rows_per_sample : 1), (bf16_t*)dbranch, ws, M, (int)N, dout_rows);
+  op_with_bool(skip_zero_rows != 0 && rowscale != nullptr, [&](auto skip) {
+    hipLaunchKernelGGL(resid_bwd_kernel<decltype(skip)::value>, dim3(ceil_div(N, 512), parts), dim3(256), 0, s, (const bf16_t*)dout,
+                       (const bf16_t*)(dgamma ? y : nullptr), (const bf16_t*)(g0 ? nullptr : gamma), rowscale,
+                       (int)(rows_per_sample > 0 ? rows_per_sample : 1), (bf16_t*)dbranch, ws, M, (int)N, dout_rows);
+    return OP_OK;
+  });
   OP_LAUNCH_CHECK();
   if (ws) {
     // job 0: dgamma from sum rs*dout*y; job 1: dbias = gamma * sum rs*dout; job 2 (g0): the same partials without gamma, fp32
@@ -1017,6 +1039,23 @@ int op_resid_bwd(const void* dout, const void* y, const void* gamma, const float
     OP_LAUNCH_CHECK();
   }
   return OP_OK;
+}
+
+int op_resid_bwd(const void* dout, const void* y, const void* gamma, const float* rowscale, int64_t rows_per_sample,
+                 void* dbranch, void* dgamma, void* dbias, float* g0, void* workspace, int64_t M, int64_t N, int accumulate,
+                 const int* dout_rows, void* stream) {
+  return resid_bwd_impl(dout, y, gamma, rowscale, rows_per_sample, dbranch, dgamma, dbias, g0, workspace, M, N, accumulate, dout_rows, 0,
+                        stream);
+}
+
+// (additive: op_abi_version() stays 10) op_resid_bwd that does not read the rows its multiplier zeroes: where rowscale[m / rps] == 0
+// nothing of dout / y is loaded, dbranch gets +0 and the column sums no contribution (op_resid_bwd: +-0 * dout, NaN for a non-finite
+// dout).  Every other row and the column sums have op_resid_bwd's bits.  rowscale null: op_resid_bwd.
+int op_resid_bwd_skip(const void* dout, const void* y, const void* gamma, const float* rowscale, int64_t rows_per_sample,
+                      void* dbranch, void* dgamma, void* dbias, float* g0, void* workspace, int64_t M, int64_t N, int accumulate,
+                      const int* dout_rows, void* stream) {
+  return resid_bwd_impl(dout, y, gamma, rowscale, rows_per_sample, dbranch, dgamma, dbias, g0, workspace, M, N, accumulate, dout_rows, 1,
+                        stream);
 }
 
 // dgamma[n] (+)= sum_s rowdot[s][n] + sum_i b_i[n] * g0_i[n]  (see include/onepeace_hip.h)

@@ -189,18 +189,28 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
 // per element, 13 % of the fused-epilogue GEMM: one wave per SIMD cannot hide it) out of the GEMM's epilogue and into a kernel
 // that is HBM-bound with VALU to spare; the product is rounded to bf16 before the statistics, exactly as the backward
 // (ln_geglu_bwd_kernel) re-creates it.  Algorithmic bytes: 2 reads + 1 write of [rows, cols] bf16.
-template <int CH, int NW, bool Q8 = false>  // Q8: see ln_fwd_kernel
+// SKIP (never with Q8): row r belongs to sample r / rps, and a row whose sample has the stochastic-depth multiplier ps == 0 is DROPPED:
+// nothing of it is loaded (h0 | h1 may hold anything there, NaN included), y gets +0 and mean / rstd are left alone -- every reader of
+// that y row multiplies it by an exact zero, and the backward skips the row by the same rule.  The rule of a row is read before the
+// row's loads are issued (one trip ahead of them); it is the same for all threads that share a barrier (NW == 4: the
+// workgroup walks one row; NW == 1: the reductions are wave-level and a wave walks one row).
+template <int CH, int NW, bool Q8 = false, bool SKIP = false>  // Q8: see ln_fwd_kernel
 __global__ __launch_bounds__(NW == 1 ? 256 : 64 * NW) void ln_geglu_fwd_kernel(const bf16_t* __restrict__ h0, const bf16_t* __restrict__ h1,
                                                            int64_t ldh, const bf16_t* __restrict__ w, const bf16_t* __restrict__ b,
                                                            bf16_t* __restrict__ y, float* __restrict__ mean_out,
                                                            float* __restrict__ rstd_out, int64_t rows, int cols, float eps,
-                                                           uint8_t* __restrict__ q8 = nullptr, float* __restrict__ q8_scale = nullptr) {
+                                                           uint8_t* __restrict__ q8 = nullptr, float* __restrict__ q8_scale = nullptr,
+                                                           const float* __restrict__ ps = nullptr, int rps = 1) {
+  static_assert(!(Q8 && SKIP), "the fp8 route runs every row");
   __shared__ float red[4];
   constexpr int G = 64 * NW;
   const int tig = (NW == 1) ? (threadIdx.x & 63) : threadIdx.x;
-  const int64_t row0 = (NW == 1) ? ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) : blockIdx.x;
+  // (SKIP: the wave index as a scalar, so that the walk and its multipliers stay in scalar registers)
+  const int wave = SKIP ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
+  const int64_t row0 = (NW == 1) ? ((int64_t)blockIdx.x * 4 + wave) : blockIdx.x;
   const int64_t rstep = (NW == 1) ? (int64_t)gridDim.x * 4 : gridDim.x;
   const float inv = 1.0f / (float)cols;
+  auto ps_of = [&](int64_t r) { return ps[(uint32_t)r / (uint32_t)rps]; };  // (SKIP; the host checks rows < 2^31)
   float wv[CH][8], bv[CH][8];
 #pragma unroll
   for (int i = 0; i < CH; ++i) {
@@ -213,18 +223,44 @@ __global__ __launch_bounds__(NW == 1 ? 256 : 64 * NW) void ln_geglu_fwd_kernel(c
     }
   }
   bf16x8 c0[CH], c1[CH], n0[CH], n1[CH];
-  if (row0 < rows) {
+  // The walk: next_live() gives the next row of this wave / workgroup that is not dropped (every row without SKIP); the dropped rows
+  // on the way get their +0 here.  The multiplier of the row AFTER the one returned is requested at once and used a trip later, so
+  // only a run of dropped rows waits for its loads.
+  int64_t rahead = row0;
+  float pahead = 1.f;
+  if constexpr (SKIP) pahead = row0 < rows ? ps_of(row0) : 1.f;
+  auto next_live = [&]() {
+    int64_t r = rahead;
+    if constexpr (SKIP) {
+      float p = pahead;
+      while (r < rows && p == 0.f) {  // (uniform over the threads that share a barrier: no barrier inside, the same trips outside)
+        const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+          const int c = (tig + G * i) * 8;
+          if (c < cols) Vec8<bf16_t>::store_nt(y + r * (int64_t)cols + c, z);
+        }
+        r += rstep;
+        p = r < rows ? ps_of(r) : 1.f;
+      }
+      pahead = r + rstep < rows ? ps_of(r + rstep) : 1.f;
+    }
+    rahead = r + rstep;
+    return r;
+  };
+  const int64_t first = next_live();
+  if (first < rows) {
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = (tig + G * i) * 8;
       if (c < cols) {
-        c0[i] = Vec8<bf16_t>::ldraw_nt(h0 + row0 * ldh + c);
-        c1[i] = Vec8<bf16_t>::ldraw_nt(h1 + row0 * ldh + c);
+        c0[i] = Vec8<bf16_t>::ldraw_nt(h0 + first * ldh + c);
+        c1[i] = Vec8<bf16_t>::ldraw_nt(h1 + first * ldh + c);
       }
     }
   }
-  for (int64_t row = row0; row < rows; row += rstep) {
-    const int64_t nrow = row + rstep;
+  for (int64_t row = first; row < rows;) {
+    const int64_t nrow = next_live();  // (known before the next row's loads are issued)
     if (nrow < rows) {
 #pragma unroll
       for (int i = 0; i < CH; ++i) {
@@ -298,18 +334,23 @@ __global__ __launch_bounds__(NW == 1 ? 256 : 64 * NW) void ln_geglu_fwd_kernel(c
     }
 #pragma unroll
     for (int i = 0; i < CH; ++i) { c0[i] = n0[i]; c1[i] = n1[i]; }
+    row = nrow;
   }
 }
 
 // dx = rstd * (dy*w - mean(dy*w) - xhat * mean(dy*w*xhat));  dw = sum_rows dy*xhat;  db = sum_rows dy.
 // Partial dw/db of each workgroup go to ws[gridDim.x][2][cols] (fp32); ln_bwd_reduce_kernel folds them.
-template <typename T, int CH, int NW, bool GELU, bool NT>
+// SKIP (see ln_geglu_fwd_kernel; never with xmap): a dropped row has an exact-zero dy row in the dense step; nothing of dy, x, mean and
+// rstd is loaded for it, dx gets +0 -- or, with `add`, the 16-byte copies of the add row (nothing at all where dx IS add) -- and dw / db
+// get nothing from it.
+template <typename T, int CH, int NW, bool GELU, bool NT, bool SKIP = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ x,
                                                      const T* __restrict__ w, const T* __restrict__ b,
                                                      const float* __restrict__ mean_in,
                                                      const float* __restrict__ rstd_in, const T* __restrict__ add,
                                                      T* __restrict__ dx, float* __restrict__ ws, int64_t rows, int cols,
-                                                     const int* __restrict__ xmap = nullptr) {
+                                                     const int* __restrict__ xmap = nullptr, const float* __restrict__ ps = nullptr,
+                                                     int rps = 1) {
   // xmap (nullable, ABI 9; see ln_fwd_kernel): x, add and dx are rows xmap[r] of LARGER matrices (dy / mean / rstd are indexed by r);
   // a row without a source (< 0) is a row of zeros for x, has no `add` and is not stored.  dx may be `add` (in place: only the mapped
   // rows change -- the rows of dropped samples keep the gradient of the skip connection).
@@ -317,7 +358,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
   float* red = smem;
   constexpr int G = 64 * NW;
   const int tig = (NW == 1) ? (threadIdx.x & 63) : threadIdx.x;
-  const int wid = threadIdx.x >> 6;
+  const int wid = SKIP ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);  // (SKIP: a scalar, see ln_geglu_fwd_kernel)
   const int64_t row0 = (NW == 1) ? ((int64_t)blockIdx.x * 4 + wid) : blockIdx.x;
   const int64_t rstep = (NW == 1) ? (int64_t)gridDim.x * 4 : gridDim.x;
   const float inv = 1.0f / (float)cols;
@@ -335,23 +376,56 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
   }
   typedef typename Vec8<T>::raw_t raw_t;
   raw_t curx[CH], curg[CH], nxtx[CH], nxtg[CH], addv[CH];
+  // The walk (see ln_geglu_fwd_kernel): the next row that is not dropped; the dropped rows on the way get their dx here
+  auto ps_of = [&](int64_t r) { return ps[(uint32_t)r / (uint32_t)rps]; };  // (SKIP; the host checks rows < 2^31)
+  int64_t rahead = row0;
+  float pahead = 1.f;
+  if constexpr (SKIP) pahead = row0 < rows ? ps_of(row0) : 1.f;
+  auto next_live = [&]() {
+    int64_t r = rahead;
+    if constexpr (SKIP) {
+      float p = pahead;
+      while (r < rows && p == 0.f) {  // (uniform over the threads that share a barrier: no barrier inside, the same trips outside)
+        if (add != dx) {
+#pragma unroll
+          for (int i = 0; i < CH; ++i) {
+            const int c = (tig + G * i) * 8;
+            if (c < cols) {
+              raw_t v = raw_t{};
+              if (add) v = ldraw_sel<T, NT>(add + r * (int64_t)cols + c);
+              *reinterpret_cast<raw_t*>(dx + r * (int64_t)cols + c) = v;
+            }
+          }
+        }
+        r += rstep;
+        p = r < rows ? ps_of(r) : 1.f;
+      }
+      pahead = r + rstep < rows ? ps_of(r + rstep) : 1.f;
+    }
+    rahead = r + rstep;
+    return r;
+  };
+  int64_t first = row0;  // (without SKIP the walk is row0, row0 + rstep, ...: none of the state above is live)
+  if constexpr (SKIP) first = next_live();
   // (uniform per row group; the entry of row r + 2 steps is requested while row r is computed: see ln_fwd_kernel)
-  int64_t src = row0 < rows ? (xmap ? (int64_t)xmap[row0] : row0) : -1;
-  int64_t nsrc = row0 + rstep < rows ? (xmap ? (int64_t)xmap[row0 + rstep] : row0 + rstep) : -1, nnsrc = -1;
-  if (row0 < rows) {
+  int64_t src = first < rows ? (xmap ? (int64_t)xmap[first] : first) : -1;
+  int64_t nsrc = first + rstep < rows ? (xmap ? (int64_t)xmap[first + rstep] : first + rstep) : -1, nnsrc = -1;
+  if (first < rows) {
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = (tig + G * i) * 8;
       if (c < cols) {
         if (src >= 0) curx[i] = ldraw_sel<T, NT>(x + src * (int64_t)cols + c);
         else curx[i] = raw_t{};
-        curg[i] = ldraw_sel<T, NT>(dy + row0 * (int64_t)cols + c);
+        curg[i] = ldraw_sel<T, NT>(dy + first * (int64_t)cols + c);
       }
     }
   }
-  for (int64_t row = row0; row < rows; row += rstep) {
+  for (int64_t row = first; row < rows;) {
     const float mean = mean_in[row], rstd = rstd_in[row];
-    const int64_t nrow = row + rstep, nnrow = nrow + rstep;
+    int64_t nrow = row + rstep;
+    if constexpr (SKIP) nsrc = nrow = next_live();  // (known before the next row's loads are issued; no row table)
+    const int64_t nnrow = nrow + rstep;
     if (nnrow < rows) nnsrc = xmap ? (int64_t)xmap[nnrow] : nnrow;
 #pragma unroll
     for (int i = 0; i < CH; ++i) {  // residual-path gradient of this row + both operands of the next row
@@ -409,6 +483,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
     for (int i = 0; i < CH; ++i) { curx[i] = nxtx[i]; curg[i] = nxtg[i]; }
     src = nsrc;
     nsrc = nnsrc;
+    row = nrow;
   }
   if (ws == nullptr) return;  // uniform
   float* wsb = ws + (int64_t)blockIdx.x * 2 * cols;
@@ -446,21 +521,24 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
 //   dg  = rstd * (dy*w - mean(dy*w) - xhat * mean(dy*w*xhat)),   xhat = (g - mean) * rstd
 //   dh0 = dg * h1 * gelu'(h0),   dh1 = dg * gelu(h0)
 // Algorithmic bytes: 3 reads + 2 writes of [rows, cols] bf16 (the unfused pair moved 8 passes).
-template <int CH, int NW>
+// SKIP (see ln_geglu_fwd_kernel): a dropped row has an exact-zero dy row in the dense step; nothing of it is loaded (dy, h0 | h1, mean,
+// rstd), dh0 | dh1 get +0 and dw / db get nothing from it.
+template <int CH, int NW, bool SKIP = false>
 __global__ __launch_bounds__(NW == 1 ? 256 : 64 * NW) void ln_geglu_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ h0,
                                                            const bf16_t* __restrict__ h1, const bf16_t* __restrict__ w,
                                                            const float* __restrict__ mean_in,
                                                            const float* __restrict__ rstd_in, bf16_t* __restrict__ dh0,
                                                            bf16_t* __restrict__ dh1, int64_t ldd, int64_t ldh, float* __restrict__ ws,
-                                                           int64_t rows, int cols) {
+                                                           int64_t rows, int cols, const float* __restrict__ ps = nullptr, int rps = 1) {
   extern __shared__ __attribute__((aligned(16))) float smem[];  // NW==1: [4][cols] ; NW==4: [4]
   float* red = smem;
   constexpr int G = 64 * NW;
   const int tig = (NW == 1) ? (threadIdx.x & 63) : threadIdx.x;
-  const int wid = threadIdx.x >> 6;
+  const int wid = SKIP ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);  // (SKIP: a scalar, see ln_geglu_fwd_kernel)
   const int64_t row0 = (NW == 1) ? ((int64_t)blockIdx.x * 4 + wid) : blockIdx.x;
   const int64_t rstep = (NW == 1) ? (int64_t)gridDim.x * 4 : gridDim.x;
   const float inv = 1.0f / (float)cols;
+  auto ps_of = [&](int64_t r) { return ps[(uint32_t)r / (uint32_t)rps]; };  // (SKIP; the host checks rows < 2^31)
   float dwa[CH][8], dba[CH][8];
   bf16x8 wraw[CH];  // the LayerNorm weight stays packed (4 registers per 8 columns; unpacked where it is used: one VALU op per element)
 #pragma unroll
@@ -475,21 +553,47 @@ __global__ __launch_bounds__(NW == 1 ? 256 : 64 * NW) void ln_geglu_bwd_kernel(c
   // Registers (<= 256 for two waves per SIMD): the row is kept as raw bf16 (h0, h1) + fp32 dy*w, Phi(h0) and gelu'(h0) across the two
   // block reductions, so that the NEXT row's three operands can already be in flight.
   bf16x8 r0[CH], r1[CH], rg[CH], n0[CH], n1[CH], ng[CH];
-  if (row0 < rows) {
+  // The walk (see ln_geglu_fwd_kernel): the next row that is not dropped; the dropped rows on the way get their +0 here
+  int64_t rahead = row0;
+  float pahead = 1.f;
+  if constexpr (SKIP) pahead = row0 < rows ? ps_of(row0) : 1.f;
+  auto next_live = [&]() {
+    int64_t r = rahead;
+    if constexpr (SKIP) {
+      float p = pahead;
+      while (r < rows && p == 0.f) {  // (uniform over the threads that share a barrier: no barrier inside, the same trips outside)
+        const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < CH; ++i) {
+          const int c = (tig + G * i) * 8;
+          if (c < cols) {
+            Vec8<bf16_t>::store_nt(dh0 + r * ldd + c, z);
+            Vec8<bf16_t>::store_nt(dh1 + r * ldd + c, z);
+          }
+        }
+        r += rstep;
+        p = r < rows ? ps_of(r) : 1.f;
+      }
+      pahead = r + rstep < rows ? ps_of(r + rstep) : 1.f;
+    }
+    rahead = r + rstep;
+    return r;
+  };
+  const int64_t first = next_live();
+  if (first < rows) {
 #pragma unroll
     for (int i = 0; i < CH; ++i) {
       const int c = (tig + G * i) * 8;
       if (c < cols) {
-        r0[i] = Vec8<bf16_t>::ldraw_nt(h0 + row0 * ldh + c);
-        r1[i] = Vec8<bf16_t>::ldraw_nt(h1 + row0 * ldh + c);
-        rg[i] = Vec8<bf16_t>::ldraw_nt(dy + row0 * (int64_t)cols + c);
+        r0[i] = Vec8<bf16_t>::ldraw_nt(h0 + first * ldh + c);
+        r1[i] = Vec8<bf16_t>::ldraw_nt(h1 + first * ldh + c);
+        rg[i] = Vec8<bf16_t>::ldraw_nt(dy + first * (int64_t)cols + c);
       }
     }
   }
-  for (int64_t row = row0; row < rows; row += rstep) {
+  for (int64_t row = first; row < rows;) {
     const float mean = mean_in[row], rstd = rstd_in[row];
-    const int64_t base = row * (int64_t)cols;
-    const int64_t nrow = row + rstep;
+    const int64_t nrow = next_live();  // (known before the next row's loads are issued)
     if (nrow < rows) {
 #pragma unroll
       for (int i = 0; i < CH; ++i) {
@@ -557,6 +661,7 @@ __global__ __launch_bounds__(NW == 1 ? 256 : 64 * NW) void ln_geglu_bwd_kernel(c
     }
 #pragma unroll
     for (int i = 0; i < CH; ++i) { r0[i] = n0[i]; r1[i] = n1[i]; rg[i] = ng[i]; }
+    row = nrow;
   }
   if (ws == nullptr) return;  // uniform
   float* wsb = ws + (int64_t)blockIdx.x * 2 * cols;
@@ -657,10 +762,10 @@ int ln_reduce_dw_db(float* ws, void* dw, void* db, int grid, int cols, int accum
   return OP_OK;
 }
 
-template <typename T, bool GELU>
+template <typename T, bool GELU, bool SKIP = false>  // SKIP: rows of samples with ps == 0 are not read (see ln_bwd_kernel)
 int ln_bwd_dispatch(const void* dy, const void* x, const void* w, const void* b, const float* mean, const float* rstd,
                     const void* add, void* dx, void* dw, void* db, float* ws, int64_t rows, int cols, int accumulate,
-                    hipStream_t s, const int* xmap) {
+                    hipStream_t s, const int* xmap, const float* ps = nullptr, int rps = 1) {
   float* wsk = (dw || db) ? ws : nullptr;
   const bool nt = ln_streams(rows, cols, sizeof(T));
   return ln_with_route(cols, [&](auto ch, auto nw) {
@@ -668,8 +773,8 @@ int ln_bwd_dispatch(const void* dy, const void* x, const void* w, const void* b,
     const int grid = ln_grid(rows, NW, g_ln_blocks_bwd);
     const size_t sh = (NW == 1) ? (size_t)4 * cols * sizeof(float) : 64;
     const int rc = op_with_bool(nt, [&](auto ntc) {
-      hipLaunchKernelGGL((ln_bwd_kernel<T, CH, NW, GELU, decltype(ntc)::value>), dim3(grid), dim3(256), sh, s, (const T*)dy, (const T*)x,
-                         (const T*)w, (const T*)b, mean, rstd, (const T*)add, (T*)dx, wsk, rows, cols, xmap);
+      hipLaunchKernelGGL((ln_bwd_kernel<T, CH, NW, GELU, decltype(ntc)::value, SKIP>), dim3(grid), dim3(256), sh, s, (const T*)dy, (const T*)x,
+                         (const T*)w, (const T*)b, mean, rstd, (const T*)add, (T*)dx, wsk, rows, cols, xmap, ps, rps);
       OP_LAUNCH_CHECK();
       return OP_OK;
     });
@@ -677,16 +782,33 @@ int ln_bwd_dispatch(const void* dy, const void* x, const void* w, const void* b,
   });
 }
 
-template <bool Q8>
+template <bool Q8, bool SKIP = false>  // SKIP: rows of samples with ps == 0 are not read (see ln_geglu_fwd_kernel)
 int ln_geglu_fwd_dispatch(const void* h0, const void* h1, int64_t ldh, const void* w, const void* b, void* y, float* mean, float* rstd,
-                          void* q8, float* q8_scale, int64_t rows, int cols, float eps, hipStream_t s) {
+                          void* q8, float* q8_scale, int64_t rows, int cols, float eps, hipStream_t s, const float* ps = nullptr,
+                          int rps = 1) {
   return ln_with_route(cols, [&](auto ch, auto nw) {
     constexpr int CH = decltype(ch)::value, NW = decltype(nw)::value;
-    hipLaunchKernelGGL((ln_geglu_fwd_kernel<CH, NW, Q8>), dim3(ln_grid(rows, NW, OP_LN_GEGLU_BLOCKS_FWD)), dim3(NW == 1 ? 256 : 64 * NW), 0,
+    hipLaunchKernelGGL((ln_geglu_fwd_kernel<CH, NW, Q8, SKIP>), dim3(ln_grid(rows, NW, OP_LN_GEGLU_BLOCKS_FWD)), dim3(NW == 1 ? 256 : 64 * NW), 0,
                        s, (const bf16_t*)h0, (const bf16_t*)h1, ldh, (const bf16_t*)w, (const bf16_t*)b, (bf16_t*)y, mean, rstd, rows,
-                       cols, eps, (uint8_t*)q8, q8_scale);
+                       cols, eps, (uint8_t*)q8, q8_scale, ps, rps);
     OP_LAUNCH_CHECK();
     return OP_OK;
+  });
+}
+
+template <bool SKIP>
+int ln_geglu_bwd_dispatch(const void* dy, const void* h0, const void* h1, const void* w, const float* mean, const float* rstd, void* dh0,
+                          void* dh1, int64_t ldd, int64_t ldh, void* dw, void* db, float* wsk, int64_t rows, int cols, int accumulate,
+                          hipStream_t s, const float* ps = nullptr, int rps = 1) {
+  return ln_with_route(cols, [&](auto ch, auto nw) {
+    constexpr int CH = decltype(ch)::value, NW = decltype(nw)::value;
+    const int grid = ln_grid(rows, NW, OP_LN_GEGLU_BLOCKS_BWD);
+    const size_t sh = (NW == 1) ? (size_t)4 * cols * sizeof(float) : 64;
+    hipLaunchKernelGGL((ln_geglu_bwd_kernel<CH, NW, SKIP>), dim3(grid), dim3(NW == 1 ? 256 : 64 * NW), sh, s, (const bf16_t*)dy,
+                       (const bf16_t*)h0, (const bf16_t*)h1, (const bf16_t*)w, mean, rstd, (bf16_t*)dh0, (bf16_t*)dh1, ldd, ldh, wsk,
+                       rows, cols, ps, rps);
+    OP_LAUNCH_CHECK();
+    return wsk ? ln_reduce_dw_db<bf16_t>(wsk, dw, db, grid, cols, accumulate, s) : OP_OK;
   });
 }
 
@@ -745,6 +867,25 @@ int op_layernorm_bwd(const void* dy, const void* x, const void* w, const void* b
   });
 }
 
+// (additive: op_abi_version() stays 10) op_layernorm_bwd for bf16 without GELU and without a row table that leaves out the rows of the
+// samples stochastic depth dropped (see op_ln_geglu_fwd_skip for ps / rows_per_sample): nothing of dy, x, mean and rstd is read for such
+// a row; dx gets +0 there, or with `add` the bits of the add row (dx may be add itself); dw / db get no contribution -- what
+// op_layernorm_bwd gives for the exact-zero dy row the dense step has there, up to the sign of a zero in add.  Every other row, dw and
+// db have op_layernorm_bwd's bits.  ps null: op_layernorm_bwd.
+int op_layernorm_bwd_skip(const void* dy, const void* x, const void* w, const float* mean, const float* rstd, const void* add, void* dx,
+                          void* dw, void* db, void* workspace, int64_t rows, int64_t cols, int accumulate, const float* ps,
+                          int64_t rows_per_sample, void* stream) {
+  if (!ps) return op_layernorm_bwd(dy, x, w, nullptr, mean, rstd, add, dx, dw, db, workspace, rows, cols, 0, accumulate, OP_DT_BF16, nullptr, stream);
+  OP_CHECK_ARG(dy && x && dx && mean && rstd, "layernorm_bwd_skip: null pointer");
+  OP_CHECK_ARG(rows >= 0 && cols > 0 && cols % 8 == 0, "layernorm_bwd_skip: cols=%lld must be a positive multiple of 8", (long long)cols);
+  OP_CHECK_ARG(!(dw || db) || workspace, "layernorm_bwd_skip: dw/db requested without workspace");
+  OP_CHECK_ARG(rows < ((int64_t)1 << 31) && rows_per_sample >= 1 && rows_per_sample < ((int64_t)1 << 31),
+               "layernorm_bwd_skip: rows=%lld rows_per_sample=%lld", (long long)rows, (long long)rows_per_sample);
+  if (rows == 0) return OP_OK;
+  return ln_bwd_dispatch<bf16_t, false, true>(dy, x, w, nullptr, mean, rstd, add, dx, dw, db, (float*)workspace, rows, (int)cols, accumulate,
+                                              (hipStream_t)stream, nullptr, ps, (int)rows_per_sample);
+}
+
 // y [rows, cols] = LayerNorm(bf16(gelu(h0) * h1)) (+ mean / rstd, nullable); h0, h1: row stride ldh (0 = cols).
 int op_ln_geglu_fwd(const void* h0, const void* h1, int64_t ldh, const void* w, const void* b, void* y, float* mean, float* rstd,
                     int64_t rows, int64_t cols, float eps, void* stream) {
@@ -780,18 +921,46 @@ int op_ln_geglu_bwd(const void* dy, const void* h0, const void* h1, const void* 
   OP_CHECK_ARG(rows >= 0 && cols > 0 && cols % 8 == 0 && cols <= 8192, "ln_geglu_bwd: cols=%lld unsupported", (long long)cols);
   OP_CHECK_ARG(!(dw || db) || workspace, "ln_geglu_bwd: dw/db requested without workspace");
   if (rows == 0) return OP_OK;
-  hipStream_t s = (hipStream_t)stream;
   float* wsk = (dw || db) ? (float*)workspace : nullptr;
-  return ln_with_route((int)cols, [&](auto ch, auto nw) {
-    constexpr int CH = decltype(ch)::value, NW = decltype(nw)::value;
-    const int grid = ln_grid(rows, NW, OP_LN_GEGLU_BLOCKS_BWD);
-    const size_t sh = (NW == 1) ? (size_t)4 * cols * sizeof(float) : 64;
-    hipLaunchKernelGGL((ln_geglu_bwd_kernel<CH, NW>), dim3(grid), dim3(NW == 1 ? 256 : 64 * NW), sh, s, (const bf16_t*)dy,
-                       (const bf16_t*)h0, (const bf16_t*)h1, (const bf16_t*)w, mean, rstd, (bf16_t*)dh0, (bf16_t*)dh1, ldd, ldh, wsk,
-                       rows, (int)cols);
-    OP_LAUNCH_CHECK();
-    return wsk ? ln_reduce_dw_db<bf16_t>(wsk, dw, db, grid, (int)cols, accumulate, s) : OP_OK;
-  });
+  return ln_geglu_bwd_dispatch<false>(dy, h0, h1, w, mean, rstd, dh0, dh1, ldd, ldh, dw, db, wsk, rows, (int)cols, accumulate,
+                                      (hipStream_t)stream);
+}
+
+// (additive: op_abi_version() stays 10) op_ln_geglu_fwd / op_ln_geglu_bwd that leave out the rows of the samples stochastic depth
+// dropped: row r belongs to sample r / rows_per_sample (>= 1; a per-row vector: 1), and where ps[sample] == 0 NOTHING of the row is
+// read -- h0 | h1 (and dy, mean, rstd in backward) may hold anything there.  Forward: y gets +0 in such a row, mean / rstd are not
+// written.  Backward: dh0 | dh1 get +0, dw / db get no contribution -- what the plain entry gives for the exact-zero dy row the dense
+// step has there.  Every other row has the plain entry's bits, and so have dw / db.  ps null: the plain entry.  rows < 2^31.
+int op_ln_geglu_fwd_skip(const void* h0, const void* h1, int64_t ldh, const void* w, const void* b, void* y, float* mean, float* rstd,
+                         int64_t rows, int64_t cols, float eps, const float* ps, int64_t rows_per_sample, void* stream) {
+  if (!ps) return op_ln_geglu_fwd(h0, h1, ldh, w, b, y, mean, rstd, rows, cols, eps, stream);
+  OP_CHECK_ARG(h0 && h1 && y, "ln_geglu_fwd_skip: null pointer");
+  if (ldh <= 0) ldh = cols;
+  OP_CHECK_ARG(rows >= 0 && cols > 0 && cols % 8 == 0 && cols <= 8192 && ldh >= cols && ldh % 8 == 0, "ln_geglu_fwd_skip: cols=%lld ldh=%lld unsupported",
+               (long long)cols, (long long)ldh);
+  OP_CHECK_ARG(rows < ((int64_t)1 << 31) && rows_per_sample >= 1 && rows_per_sample < ((int64_t)1 << 31),
+               "ln_geglu_fwd_skip: rows=%lld rows_per_sample=%lld", (long long)rows, (long long)rows_per_sample);
+  if (rows == 0) return OP_OK;
+  return ln_geglu_fwd_dispatch<false, true>(h0, h1, ldh, w, b, y, mean, rstd, nullptr, nullptr, rows, (int)cols, eps, (hipStream_t)stream,
+                                            ps, (int)rows_per_sample);
+}
+
+int op_ln_geglu_bwd_skip(const void* dy, const void* h0, const void* h1, const void* w, const float* mean, const float* rstd,
+                         void* dh0, void* dh1, int64_t ldd, int64_t ldh, void* dw, void* db, void* workspace, int64_t rows, int64_t cols,
+                         int accumulate, const float* ps, int64_t rows_per_sample, void* stream) {
+  if (!ps) return op_ln_geglu_bwd(dy, h0, h1, w, mean, rstd, dh0, dh1, ldd, ldh, dw, db, workspace, rows, cols, accumulate, stream);
+  OP_CHECK_ARG(dy && h0 && h1 && dh0 && dh1 && mean && rstd, "ln_geglu_bwd_skip: null pointer");
+  if (ldd <= 0) ldd = cols;
+  if (ldh <= 0) ldh = cols;
+  OP_CHECK_ARG(ldd >= cols && ldd % 8 == 0 && ldh >= cols && ldh % 8 == 0, "ln_geglu_bwd_skip: row strides %lld / %lld", (long long)ldd, (long long)ldh);
+  OP_CHECK_ARG(rows >= 0 && cols > 0 && cols % 8 == 0 && cols <= 8192, "ln_geglu_bwd_skip: cols=%lld unsupported", (long long)cols);
+  OP_CHECK_ARG(!(dw || db) || workspace, "ln_geglu_bwd_skip: dw/db requested without workspace");
+  OP_CHECK_ARG(rows < ((int64_t)1 << 31) && rows_per_sample >= 1 && rows_per_sample < ((int64_t)1 << 31),
+               "ln_geglu_bwd_skip: rows=%lld rows_per_sample=%lld", (long long)rows, (long long)rows_per_sample);
+  if (rows == 0) return OP_OK;
+  float* wsk = (dw || db) ? (float*)workspace : nullptr;
+  return ln_geglu_bwd_dispatch<true>(dy, h0, h1, w, mean, rstd, dh0, dh1, ldd, ldh, dw, db, wsk, rows, (int)cols, accumulate,
+                                     (hipStream_t)stream, ps, (int)rows_per_sample);
 }
 
 }  // extern "C"

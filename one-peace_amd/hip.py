@@ -61,9 +61,13 @@ SIGNATURES = {
     "op_colsum_segments": (c_int, [P, P, P, P, P, I64, I64, I64, c_int, P]),
     "op_resid_bwd_workspace_bytes": (I64, [I64]),
     "op_resid_bwd": (c_int, [P, P, P, P, I64, P, P, P, P, P, I64, I64, c_int, P, P]),
+    "op_resid_bwd_skip": (c_int, [P, P, P, P, I64, P, P, P, P, P, I64, I64, c_int, P, P]),
+    "op_layernorm_bwd_skip": (c_int, [P, P, P, P, P, P, P, P, P, P, I64, I64, c_int, P, I64, P]),
     "op_gamma_grad_finish": (c_int, [P, I64, P, P, P, P, P, P, P, I64, c_int, P]),
     "op_ln_geglu_bwd": (c_int, [P, P, P, P, P, P, P, P, I64, I64, P, P, P, I64, I64, c_int, P]),
     "op_ln_geglu_fwd": (c_int, [P, P, I64, P, P, P, P, P, I64, I64, c_float, P]),
+    "op_ln_geglu_bwd_skip": (c_int, [P, P, P, P, P, P, P, P, I64, I64, P, P, P, I64, I64, c_int, P, I64, P]),
+    "op_ln_geglu_fwd_skip": (c_int, [P, P, I64, P, P, P, P, P, I64, I64, c_float, P, I64, P]),
     "op_colsum": (c_int, [P, P, P, I64, P, P, P, I64, I64, c_int, c_int, P]),
     "op_geglu_bwd": (c_int, [P, P, P, P, P, I64, P]),
     "op_scale_rows": (c_int, [P, P, P, I64, P, I64, I64, P]),
@@ -338,9 +342,11 @@ def workspace(nbytes, device, tag="ws"):
 
 
 def layernorm_bwd(dy, x, w, b, mean, rstd, gelu=False, need_wgrad=True, dw=None, db=None, accumulate=False, add=None,
-                  dx=None, x_rows=None):
+                  dx=None, x_rows=None, ps=None, rows_per_sample=1):
     """x_rows (int32 [rows of dy]): x, add and dx are rows x_rows[r] of larger matrices; dx must be given (dx = add: in place, the
-    rows no entry names keep `add`)."""
+    rows no entry names keep `add`).
+    ps (bf16, no GELU, no x_rows; fp32, one stochastic-depth multiplier per rows_per_sample rows): the rows of samples with ps == 0 are
+    not read -- dx gets +0 there or the bits of `add`, dw / db nothing (op_layernorm_bwd_skip)."""
     rows, cols = x.shape
     if x_rows is not None:
         assert dx is not None and dx.shape == x.shape and (add is None or add.shape == x.shape) and x_rows.dtype == torch.int32
@@ -357,6 +363,12 @@ def layernorm_bwd(dy, x, w, b, mean, rstd, gelu=False, need_wgrad=True, dw=None,
         ws = workspace(lib().op_layernorm_bwd_workspace_bytes(rows, cols), x.device, "ln")
     else:
         dw = db = None
+    if ps is not None:
+        assert x.dtype == torch.bfloat16 and not gelu and x_rows is None
+        _check(lib().op_layernorm_bwd_skip(ptr(dy), ptr(x), ptr(w), ptr(mean), ptr(rstd), ptr(add), ptr(dx), ptr(dw), ptr(db), ptr(ws), rows,
+                                           cols, int(accumulate), *_skip_args(ps, rows_per_sample, rows, x.device), stream()),
+               "op_layernorm_bwd_skip")
+        return dx, dw, db
     _check(lib().op_layernorm_bwd(ptr(dy), ptr(x), ptr(w), ptr(b), ptr(mean), ptr(rstd), ptr(add), ptr(dx), ptr(dw), ptr(db),
                                   ptr(ws), rows, cols, int(gelu), int(accumulate), _dt(x), ptr(x_rows), stream()), "op_layernorm_bwd")
     return dx, dw, db
@@ -662,9 +674,13 @@ def _live_mwindows(segs, lists, outs, _srcs):
 
 def live_mwindows_fwd(segs, lists, outs, srcs):
     """live_mwindows for the FORWARD launches of a residual branch (gemm_nt_windows_fwd): the same lists; the rows of outs[o] that no window
-    covers get a copy of the same rows of srcs[o] (the residual output takes the residual input) or, with srcs[o] None, +0."""
-    assert len(outs) >= 1 and len(srcs) == len(outs)
-    return _live_mwindows(segs, lists, outs, list(srcs))
+    covers get a copy of the same rows of srcs[o] (the residual output takes the residual input) or, with srcs[o] None, +0.
+    An entry of outs may be None: a matrix of the branch that gets NO fill, because every reader of its rows leaves out the rows of
+    dropped samples (h0 | h1 under ops.SKIP_ZERO_ROWS); the launch does not hear of it."""
+    assert len(srcs) == len(outs)
+    pairs = [(o, q) for o, q in zip(outs, srcs) if o is not None]
+    assert len(pairs) >= 1
+    return _live_mwindows(segs, lists, [o for o, _ in pairs], [q for _, q in pairs])
 
 
 def gemm_nt_windows_fwd(As, Wss, biases, outs, windows, n_seg, epilogue=EPI_BIAS, resids=None, gammas=None, rowscales=None,
@@ -835,11 +851,12 @@ def colsum_segments(x, seg_cols, outs=None, accumulate=False):
 
 
 def resid_bwd(dout, y=None, gamma=None, rowscale=None, rows_per_sample=0, dgamma=None, dbias=None, accumulate=False, g0=None,
-              dout_rows=None):
+              dout_rows=None, skip_zero_rows=False):
     """dbranch = rowscale*gamma*dout plus the column reductions dgamma / dbias in one pass.  dgamma / dbias: True
     (allocate), a bf16 [N] tensor (write or, with accumulate, add into it) or None (skip).  g0: fp32 [N] that receives
     sum_m rowscale*dout (dbias without the gamma factor: gamma_grad_finish's operand) -- and dbranch is then rowscale*dout WITHOUT
-    gamma (the weight-gradient launch's rscale and the gamma-scaled transposed weight carry it)."""
+    gamma (the weight-gradient launch's rscale and the gamma-scaled transposed weight carry it).
+    skip_zero_rows: the rows whose multiplier is 0 are not read; dbranch gets +0 there (op_resid_bwd_skip)."""
     M, N = dout.shape
     if dout_rows is not None:  # dout: a larger matrix, row m of the pass = its row dout_rows[m] (< 0: zeros); the result has M rows
         assert dout_rows.dtype == torch.int32 and dout_rows.is_contiguous() and dout.is_contiguous()
@@ -854,9 +871,10 @@ def resid_bwd(dout, y=None, gamma=None, rowscale=None, rows_per_sample=0, dgamma
         ws = workspace(lib().op_resid_bwd_workspace_bytes(N), dout.device, "resid")
     assert g0 is None or (g0.dtype == torch.float32 and g0.is_contiguous() and g0.numel() == N)
     # (M = 0: g0 and the non-accumulating dgamma / dbias come back as zeros, the sums over no rows)
-    _check(lib().op_resid_bwd(_ptr_rows(dout, ws), _ptr_rows(y if dgamma is not None else None, ws), ptr(gamma), _ptr_rows(rowscale, ws),
-                              rows_per_sample, _ptr_rows(out, ws), ptr(dgamma), ptr(dbias), ptr(g0), ptr(ws), M, N, int(accumulate),
-                              _ptr_rows(dout_rows, ws), stream()), "op_resid_bwd")
+    entry = "op_resid_bwd_skip" if skip_zero_rows and rowscale is not None else "op_resid_bwd"
+    _check(getattr(lib(), entry)(_ptr_rows(dout, ws), _ptr_rows(y if dgamma is not None else None, ws), ptr(gamma), _ptr_rows(rowscale, ws),
+              rows_per_sample, _ptr_rows(out, ws), ptr(dgamma), ptr(dbias), ptr(g0), ptr(ws), M, N, int(accumulate),
+              _ptr_rows(dout_rows, ws), stream()), entry)
     return out, dgamma, dbias
 
 
@@ -874,9 +892,19 @@ def gamma_grad_finish(rowdot, pairs, dgamma, accumulate):
     return dgamma
 
 
-def ln_geglu_bwd(dy, h0, h1, w, mean, rstd, dw=None, db=None, accumulate=False, need_wgrad=True, dh0=None, dh1=None):
+def _skip_args(ps, rows_per_sample, rows, device):
+    """(ps, rows per sample) of the *_skip entries: fp32, contiguous, one multiplier for every sample the rows reach."""
+    rps = int(rows_per_sample)
+    assert rps >= 1 and ps.dtype == torch.float32 and ps.is_contiguous() and ps.device == device and ps.numel() * rps >= rows
+    return ptr(ps), rps
+
+
+def ln_geglu_bwd(dy, h0, h1, w, mean, rstd, dw=None, db=None, accumulate=False, need_wgrad=True, dh0=None, dh1=None, ps=None,
+                 rows_per_sample=1):
     """Backward of LayerNorm_F(gelu(h0)*h1): returns dh0, dh1, dw, db (dw/db allocated unless given; None with need_wgrad=False).
-    dh0 / dh1 may be given as column blocks of one wider matrix (same row stride, last dim contiguous)."""
+    dh0 / dh1 may be given as column blocks of one wider matrix (same row stride, last dim contiguous).
+    ps (fp32, one stochastic-depth multiplier per rows_per_sample rows): the rows of samples with ps == 0 are not read -- dh0 | dh1 get
+    +0 there, dw / db nothing (op_ln_geglu_bwd_skip)."""
     rows, cols = h0.shape
     if dh0 is None:
         dh0, dh1 = torch.empty_like(h0), torch.empty_like(h1)
@@ -889,14 +917,20 @@ def ln_geglu_bwd(dy, h0, h1, w, mean, rstd, dw=None, db=None, accumulate=False, 
         ws = workspace(lib().op_layernorm_bwd_workspace_bytes(rows, cols), h0.device, "ln")
     else:
         dw = db = None
+    if ps is not None:
+        _check(lib().op_ln_geglu_bwd_skip(ptr(dy), ptr(h0), ptr(h1), ptr(w), ptr(mean), ptr(rstd), ptr(dh0), ptr(dh1), dh0.stride(0),
+                                          h0.stride(0), ptr(dw), ptr(db), ptr(ws), rows, cols, int(accumulate),
+                                          *_skip_args(ps, rows_per_sample, rows, h0.device), stream()), "op_ln_geglu_bwd_skip")
+        return dh0, dh1, dw, db
     _check(lib().op_ln_geglu_bwd(ptr(dy), ptr(h0), ptr(h1), ptr(w), ptr(mean), ptr(rstd), ptr(dh0), ptr(dh1), dh0.stride(0),
                                  h0.stride(0), ptr(dw), ptr(db), ptr(ws), rows, cols, int(accumulate), stream()), "op_ln_geglu_bwd")
     return dh0, dh1, dw, db
 
 
-def ln_geglu_fwd(h0, h1, w, b, eps=1e-5, want_stats=True, out=None, mean=None, rstd=None, q8=None):
+def ln_geglu_fwd(h0, h1, w, b, eps=1e-5, want_stats=True, out=None, mean=None, rstd=None, q8=None, ps=None, rows_per_sample=1):
     """LayerNorm_F(bf16(gelu(h0) * h1)); h0 / h1 may be column blocks of one wider matrix.  Returns y, mean, rstd.
-    q8 = (fp8 bytes [rows, cols], scales [rows]): also filled with the row-quantised output (see layernorm_fwd)."""
+    q8 = (fp8 bytes [rows, cols], scales [rows]): also filled with the row-quantised output (see layernorm_fwd).
+    ps (not with q8; see ln_geglu_bwd): the rows of samples with ps == 0 are not read -- y gets +0 there, mean / rstd are not written."""
     rows, cols = h0.shape
     assert h0.stride(0) == h1.stride(0) and h0.stride(1) == 1 and h1.stride(1) == 1
     y = out if out is not None else torch.empty(rows, cols, dtype=h0.dtype, device=h0.device)
@@ -904,9 +938,14 @@ def ln_geglu_fwd(h0, h1, w, b, eps=1e-5, want_stats=True, out=None, mean=None, r
         mean = torch.empty(rows, dtype=torch.float32, device=h0.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=h0.device)
     if q8 is not None:
+        assert ps is None, "the fp8 route runs every row"
         assert q8[0].is_contiguous() and q8[0].shape == (rows, cols) and y.is_contiguous()
         _check(lib().op_ln_geglu_fwd_q8(ptr(h0), ptr(h1), h0.stride(0), ptr(w), ptr(b), ptr(y), ptr(mean), ptr(rstd), ptr(q8[0]), ptr(q8[1]),
                                         rows, cols, eps, stream()), "op_ln_geglu_fwd_q8")
+        return y, mean, rstd
+    if ps is not None:
+        _check(lib().op_ln_geglu_fwd_skip(ptr(h0), ptr(h1), h0.stride(0), ptr(w), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, cols, eps,
+                                          *_skip_args(ps, rows_per_sample, rows, h0.device), stream()), "op_ln_geglu_fwd_skip")
         return y, mean, rstd
     _check(lib().op_ln_geglu_fwd(ptr(h0), ptr(h1), h0.stride(0), ptr(w), ptr(b), ptr(y), ptr(mean), ptr(rstd), rows, cols, eps, stream()),
            "op_ln_geglu_fwd")

@@ -328,19 +328,33 @@ def _dense_dgrad_sums_k_in_one_piece(M, N, K, device):
     return _dense_dgrad_plans[key]
 
 
-def _dgrad_windows(segs, lists, outs, dense):
+def _dgrad_windows(segs, lists, outs, dense, unread=()):
     """hip.live_mwindows' lists for the input gradients of a branch, or None when they do not apply: switched off, no multipliers, a
     shape the persistent kernel does not take, or a dense launch ([(M, N, K)], the per-problem launches the lists replace) that would
-    split K.  segs: [(ps, row0, S, B, ps stride)]."""
-    if not SKIP_ZERO_DGRAD or all(q[0] is None for q in segs) or len(segs) > 4 or len(lists) > 4 or len(outs) > 4:
+    split K.  segs: [(ps, row0, S, B, ps stride)].  unread: outputs whose ONLY reader leaves out the rows of dropped samples when the
+    lists apply and SKIP_ZERO_ROWS is on (the caller passes it ps) -- they get no +0 rows then; with the switch off they are filled
+    like `outs`."""
+    outs = list(outs) + ([] if SKIP_ZERO_ROWS else list(unread))
+    every = outs + (list(unread) if SKIP_ZERO_ROWS else [])
+    if not SKIP_ZERO_DGRAD or all(q[0] is None for q in segs) or len(segs) > 4 or len(lists) > 4 or len(every) > 4:
         return None
-    if any(N % 256 != 0 or K % 64 != 0 or K < 128 or not _dense_dgrad_sums_k_in_one_piece(M, N, K, outs[0].device) for M, N, K in dense):
+    if any(N % 256 != 0 or K % 64 != 0 or K < 128 or not _dense_dgrad_sums_k_in_one_piece(M, N, K, every[0].device) for M, N, K in dense):
         return None
     if any(ps is not None and (ps.dtype != torch.float32 or not ps.is_contiguous() or ps.numel() <= (B - 1) * st) for ps, _, _, B, st in segs):
         return None
-    if any(o.dtype != torch.bfloat16 or o.stride(0) % 8 != 0 or o.shape[1] % 8 != 0 for o in outs):
+    if any(o.dtype != torch.bfloat16 or o.stride(0) % 8 != 0 or o.shape[1] % 8 != 0 for o in every):
         return None
     return hip.live_mwindows(segs, lists, outs)
+
+
+def _bwd_fills(pairs):
+    """(outs, unread) of _dgrad_windows from [(output or None, does its ONLY reader take the multipliers?)]: an output whose reader
+    skips the rows of dropped samples needs no +0 rows (DESIGN.md section 4.4 has the readers).
+    Attention branch: d subLN(attn) -- the sub-LayerNorm's backward skips; without a sub-LayerNorm the dense attention backward reads
+    it --, d LN1(x) -- LN1's backward skips.  FFN branch: d LN_F(g) -- op_ln_geglu_bwd skips; without LN_F the dense op_geglu_bwd
+    reads it --, d LN2(x) -- LN2's backward runs over ALL rows with one (ps, rows per sample) pair: it skips in a one-segment branch."""
+    pairs = [(o, skips) for o, skips in pairs if o is not None]
+    return [o for o, skips in pairs if not skips], [o for o, skips in pairs if skips]
 
 
 def _dgrad_listed(As, Ws, outs, windows, segs):
@@ -353,10 +367,21 @@ def _dgrad_listed(As, Ws, outs, windows, segs):
 # (hip.live_mwindows_fwd: one launch per branch builds the list and FILLS the rows no window covers -- +0 in q|k|v and h0|h1, a copy of
 # the residual input in the branch output, which is what fma(0, y, res) gives).  A listed row is the dense launch's row (same operands,
 # same K order, same epilogue); a -0 element of a dropped sample's residual stays -0 where the dense epilogue can give +0, and a non-finite
-# y in a dropped row no longer becomes NaN: equal as numbers, as the backward lists.  The row kernels and attention stay dense and read
-# zeros for a dropped sample.  "0": the dense launches (A/B, tests).  Independent of SKIP_ZERO_DGRAD / SKIP_ZERO_BACKWARD.
+# y in a dropped row no longer becomes NaN: equal as numbers, as the backward lists.  Attention and the forward LayerNorms stay dense and
+# read zeros or real rows for a dropped sample; the other row kernels: SKIP_ZERO_ROWS below.  "0": the dense launches (A/B, tests).  Independent of SKIP_ZERO_DGRAD / SKIP_ZERO_BACKWARD.
 SKIP_ZERO_FWD = os.environ.get("ONEPEACE_SKIP_ZERO_FWD", "1") != "0"
 _dense_fwd_plans = {}
+# The ROW kernels between those GEMMs (LayerNorm_F(GeGLU) forward and backward, the LayerNorm backwards, op_resid_bwd) ran over every row:
+# a dropped sample's rows were zeros a fill had written for them to read, or values a later kernel multiplies by exact zeros.  "1":
+# where the window lists of a branch and direction apply, those kernels get the multipliers and read NOTHING of a dropped sample's
+# row (hip.ln_geglu_fwd / ln_geglu_bwd / layernorm_bwd: ps; hip.resid_bwd: skip_zero_rows) -- they store what the dense kernel makes of
+# the exact-zero row it would have read (+0; the residual gradient where a LayerNorm backward adds one; LN_F(GeGLU) forward +0 instead
+# of its bias row, which every reader multiplies by zero) -- and the fills no longer write the rows only such a kernel reads: h0 | h1
+# in forward, the input-gradient outputs in backward (DESIGN.md section 4.4 has the table of who writes and who reads every row).
+# Decided from shapes and flags alone, so the forward, its recomputation and the backward agree.  "0": the launches and fills as
+# before (A/B, tests).  Independent of the three switches above; never with the fp8 route, row tables (`kept`) or padded segments,
+# where the lists do not apply either.
+SKIP_ZERO_ROWS = os.environ.get("ONEPEACE_SKIP_ZERO_ROWS", "1") != "0"
 
 
 def _dense_fwd_sums_k_in_one_piece(M, N, K, epilogue, has_bias, device):
@@ -1238,7 +1263,7 @@ def _return_grads(names, params, G, direct):
     return out
 
 
-def _resid_backward(dout, y, gamma, ps, S, gname, bname, direct, G, needs, g0=None, rows=None, fold=None):
+def _resid_backward(dout, y, gamma, ps, S, gname, bname, direct, G, needs, g0=None, rows=None, fold=None, skip_zero_rows=False):
     """Gradient of  resid + ps * gamma * (y)  w.r.t. the branch output and -- where they are wanted -- gamma and the last
     Linear's bias, in one pass.  g0 (fp32 [H]): gamma's gradient is NOT taken here (no y: dgamma_from_wgrad_ok); the kernel fills g0
     with sum_m ps * dout for op_gamma_grad_finish instead and returns ps * dout WITHOUT gamma.
@@ -1251,7 +1276,7 @@ def _resid_backward(dout, y, gamma, ps, S, gname, bname, direct, G, needs, g0=No
     dgamma = (t[gname] if acc else True) if gname in t else None
     dbias = (t[bname] if acc else True) if bname in t else None
     dy, dg, db = hip.resid_bwd(dout, y if dgamma is not None else None, gamma, ps, S, dgamma=dgamma, dbias=dbias, accumulate=acc, g0=g0,
-                               dout_rows=rows)  # (rows: dout is the full matrix, the pass runs on its rows rows[m])
+                               dout_rows=rows, skip_zero_rows=skip_zero_rows)  # (rows: dout is the full matrix, the pass runs on its rows rows[m])
     if fold is not None and gname in t:
         if not acc:
             fold[gname] = fold[gname] + dg.float() if gname in fold else dg.float()
@@ -1411,31 +1436,35 @@ class AttnBranchFn(torch.autograd.Function):
         whole = rowscale is not None and kept is None and N % rps == 0 and not any(sg.pad for sg in segs) and sum(sg.rows for sg in segs) == N
         if whole:
             kt1 = _live_ktiles([(rowscale, 0, rps, N // rps)], [(0, N)], dx_mid.device)[0]
+        # the two input gradients over all rows (out-proj, q|k|v) share ONE window list; their outputs exist before it is built,
+        # because the launch that builds it also writes the zero rows.  (SKIP_ZERO_ROWS) d subLN(attn) and d LN1(x) are each read by one
+        # LayerNorm backward, which takes the multipliers; without the sub-LayerNorm the dense attention backward reads the former
+        upstream = ("ln1_w", "ln1_b", "wq", "bq", "wk", "wv", "bv", "aln_w", "aln_b")
+        need_up = need_x or any(want_dbias) or any(needs[n] for n in upstream)
+        need_dxln1 = need_x or needs["ln1_w"] or needs["ln1_b"]
+        win1, daln, dxln1 = None, None, None
+        if need_up and whole and all(sg.S % rps == 0 and sg.row0 % rps == 0 for sg in segs):
+            daln = torch.empty(N, H, dtype=dx_mid.dtype, device=dx_mid.device)
+            dxln1 = torch.empty_like(daln) if need_dxln1 else None
+            filled, unread = _bwd_fills([(daln, P["aln_w"] is not None), (dxln1, True)])
+            win1 = _dgrad_windows([(rowscale[sg.row0 // rps:], sg.row0, sg.S, sg.B, sg.S // rps) for sg in segs],
+                                  [[(i, 0, 0) for i in range(nseg)]], filled,
+                                  [(N, H, H)] + ([(N, H, 3 * H)] if need_dxln1 else []), unread=unread)
+        zr_b = SKIP_ZERO_ROWS and win1 is not None  # the row kernels of this backward leave out the rows of dropped samples
         if ctx.dg_fused:  # dy1 = rowscale * dx_mid, WITHOUT gamma_1 (weight gradient: rscale; input gradient: scaled weight copy)
             g0 = torch.empty(H, dtype=torch.float32, device=dx_mid.device)
-            dy1 = _resid_backward(dx_mid, None, P["g1"], rowscale, rps, "g1", "bo", direct, G, needs, g0=g0, rows=xmap)
+            dy1 = _resid_backward(dx_mid, None, P["g1"], rowscale, rps, "g1", "bo", direct, G, needs, g0=g0, rows=xmap, skip_zero_rows=zr_b)
             rowdot, (rd_wo,) = _rowdot_slots(dx_mid.device, [P["wo"]])
             weight_grad("wo", dy1, A["aln"], side=(P["wo"], rd_wo, P["g1"]),
                         after=_gamma_finish_hook(rowdot, direct["g1"], [(P["bo"], g0)] if P["bo"] is not None else [], True), ktiles=kt1)
             wo_t = _transposed(P["wo"], scale=P["g1"])
         else:
-            dy1 = _resid_backward(dx_mid, A["y1"], P["g1"], rowscale, rps, "g1", "bo", direct, G, needs, rows=xmap)
+            dy1 = _resid_backward(dx_mid, A["y1"], P["g1"], rowscale, rps, "g1", "bo", direct, G, needs, rows=xmap, skip_zero_rows=zr_b)
             if needs["wo"]:
                 weight_grad("wo", dy1, A["aln"], ktiles=kt1)
             wo_t = None
-        upstream = ("ln1_w", "ln1_b", "wq", "bq", "wk", "wv", "bv", "aln_w", "aln_b")
         dx = None
-        if need_x or any(want_dbias) or any(needs[n] for n in upstream):
-            # the two input gradients over all rows (out-proj, q|k|v) share ONE window list; their outputs exist before it is built,
-            # because the launch that builds it also writes the zero rows
-            need_dxln1 = need_x or needs["ln1_w"] or needs["ln1_b"]
-            win1, daln, dxln1 = None, None, None
-            if whole and all(sg.S % rps == 0 and sg.row0 % rps == 0 for sg in segs):
-                daln = torch.empty(N, H, dtype=dy1.dtype, device=dy1.device)
-                dxln1 = torch.empty_like(daln) if need_dxln1 else None
-                win1 = _dgrad_windows([(rowscale[sg.row0 // rps:], sg.row0, sg.S, sg.B, sg.S // rps) for sg in segs],
-                                      [[(i, 0, 0) for i in range(nseg)]], [daln] + ([dxln1] if need_dxln1 else []),
-                                      [(N, H, H)] + ([(N, H, 3 * H)] if need_dxln1 else []))
+        if need_up:
             wo_in = wo_t if wo_t is not None else _transposed(P["wo"])
             if win1 is None or not _dgrad_listed([dy1], [wo_in], [daln], win1[0], segs):
                 daln = hip.gemm_nt(dy1, [wo_in])
@@ -1443,7 +1472,7 @@ class AttnBranchFn(torch.autograd.Function):
                 want = needs["aln_w"] or needs["aln_b"]
                 (tw, tb), acc = _targets(direct, "aln_w", "aln_b") if want else ((None, None), False)
                 dattn, dw_, db_ = hip.layernorm_bwd(daln, A["attn"], P["aln_w"], P["aln_b"], A["mean_a"], A["rstd_a"], dw=tw, db=tb,
-                                                    accumulate=acc, need_wgrad=want)
+                                                    accumulate=acc, need_wgrad=want, ps=rowscale if zr_b else None, rows_per_sample=rps)
                 if want:
                     _finish(direct, G, ("aln_w", "aln_b"), (dw_, db_), acc)
             else:
@@ -1499,7 +1528,7 @@ class AttnBranchFn(torch.autograd.Function):
                 # samples' rows copied below)
                 dx, dw_, db_ = hip.layernorm_bwd(dxln1, x2, P["ln1_w"], P["ln1_b"], A["mean1"], A["rstd1"], add=dx_mid, dw=tw, db=tb,
                                                  accumulate=acc, need_wgrad=want, dx=torch.empty_like(dx_full) if mapped else None,
-                                                 x_rows=xmap)
+                                                 x_rows=xmap, ps=rowscale if zr_b else None, rows_per_sample=rps)
                 if want:
                     _finish(direct, G, ("ln1_w", "ln1_b"), (dw_, db_), acc)
         if dx is None and need_x:  # nothing upstream of the residual wanted a gradient: only the skip connection carries one
@@ -1541,7 +1570,7 @@ class FfnBranchMultiFn(torch.autograd.Function):
     params: ln2_w, ln2_b, g2, then (w0, w1, fln_w, fln_b, w2, b2) per segment."""
 
     @staticmethod
-    def _compute(x2, segs, pss, params, keep, want_y, grad=None, xmap=None, listed=False):
+    def _compute(x2, segs, pss, params, keep, want_y, grad=None, xmap=None, listed=False, info=None):
         """grad: the pass belongs to a training step (default: keep).  The GeGLU form is chosen by THAT, not by `keep`: with
         checkpoint_activations the forward (keep = False) and its recomputation in backward (keep = True) must run the same kernels, or
         the LayerNorm(F) statistics the gradients use are not those of the forward output.  No-grad inference keeps the fused
@@ -1549,7 +1578,9 @@ class FfnBranchMultiFn(torch.autograd.Function):
         xmap (hip.KeptRows.rowmap, not with the fp8 FFN): x2 is the FULL matrix, the branch runs on its rows xmap[r]; the returned
         `out` is a full matrix in which the rows of the kept samples are written (the others are the caller's).
         listed (the caller's flags: no `kept`, gamma_2's gradient does not need y2): the split form's wi_0 | wi_1 launches become ONE
-        grouped launch over a window list, which also serves the grouped down-projection (SKIP_ZERO_FWD)."""
+        grouped launch over a window list, which also serves the grouped down-projection (SKIP_ZERO_FWD).
+        info (a dict): info["zero_rows"] tells whether h0 | h1 went without the fill (SKIP_ZERO_ROWS): the rows of dropped samples that
+        no window covers hold NOTHING then, and every later reader of h0 | h1 has to leave them out as op_ln_geglu_fwd did here."""
         nseg = len(segs)
         shared = dict(zip(FFN_SHARED, params[:3]))
         own = [dict(zip(FFN_OWN, params[3 + 6 * i:9 + 6 * i])) for i in range(nseg)]
@@ -1580,17 +1611,21 @@ class FfnBranchMultiFn(torch.autograd.Function):
         rstd_f = torch.empty(N, dtype=torch.float32, device=dev) if (keep or split) and has_fln else None
         L = hip.lib()
         rs = [slice(sg.row0, sg.end) for sg in segs]
-        win, mrs, out, listed_up = None, 1, None, False
+        win, mrs, out, listed_up, zero_rows = None, 1, None, False, False
         if listed and split and not fp8 and xmap is None and not (keep and want_y) and nseg <= 3 and H % 256 == 0:
             wsegs = [(ps, sg.row0, sg.S, sg.B, 1) for ps, sg in zip(pss, segs)]
             dense = [(sg.rows, 2 * Fd, H, hip.EPI_BIAS, False) for sg in segs] + ([(segs[0].rows, H, Fd, hip.EPI_RESID, True)] if nseg == 1 else [])
             if _fwd_windows_apply(wsegs, 1, 2, dense, dev, flags=not any(sg.pad for sg in segs)):
                 out = torch.empty_like(x2)
-                win = hip.live_mwindows_fwd(wsegs, [[(i, i, sg.row0) for i, sg in enumerate(segs)]], [hh, out], [None, x2])[0]
+                zero_rows = SKIP_ZERO_ROWS  # (h0 | h1: only LayerNorm_F(GeGLU) forward / backward read them, and both take ps)
+                win = hip.live_mwindows_fwd(wsegs, [[(i, i, sg.row0) for i, sg in enumerate(segs)]], [None if zero_rows else hh, out],
+                                            [None, x2])[0]
                 mrs = max([sg.S for sg in segs if hip.mwindow_rule(sg.S)[1]] or [1])
                 listed_up = hip.gemm_nt_windows_fwd([xln2[r] for r in rs], [[P["w0"], P["w1"]] for P in own], None, [hh[r] for r in rs], win, Fd,
                                                     max_row_stride=mrs)
-        for sg, P in zip(segs, own):
+        if info is not None:
+            info["zero_rows"] = zero_rows
+        for sg, P, ps in zip(segs, own, pss):
             r = slice(sg.row0, sg.end)
             if split:
                 if fp8:
@@ -1599,7 +1634,7 @@ class FfnBranchMultiFn(torch.autograd.Function):
                 elif not listed_up:
                     hip.gemm_nt(xln2[r], [P["w0"], P["w1"]], n_seg=Fd, N=2 * Fd, out=hh[r])
                 hip.ln_geglu_fwd(h0[r], h1[r], P["fln_w"], P["fln_b"], out=gln[r], mean=mean_f[r], rstd=rstd_f[r],
-                                 q8=(gq[r], gs[r]) if fp8 else None)
+                                 q8=(gq[r], gs[r]) if fp8 else None, ps=ps if zero_rows else None, rows_per_sample=sg.S)
                 continue
             if fp8:
                 (w0q, w0s), (w1q, w1s) = _fp8_weight(P["w0"]), _fp8_weight(P["w1"])
@@ -1660,8 +1695,10 @@ class FfnBranchMultiFn(torch.autograd.Function):
         w2s, b2s = [params[3 + 6 * i + 4] for i in range(nseg)], [params[3 + 6 * i + 5] for i in range(nseg)]
         ctx.dg_fused = need_grad and dgamma_from_wgrad_ok([sg.rows for sg in segs], params[2], w2s, b2s, bool(needs[2]),
                                                            [bool(needs[3 + 6 * i + 4]) for i in range(nseg)])
+        info = {}
         out, acts = FfnBranchMultiFn._compute(x2, segs, pss, params, keep, bool(needs[2]) and not ctx.dg_fused, grad=bool(int(save_acts) & 2),
-                                              xmap=kept.rowmap() if mapped else None, listed=kept is None and ctx.dg_fused)
+                                              xmap=kept.rowmap() if mapped else None, listed=kept is None and ctx.dg_fused, info=info)
+        ctx.zero_rows = info["zero_rows"]
         if mapped:
             hip.rows_merge(x_full, None, kept, out=out)  # (the dropped samples' rows: copied)
         elif kept is not None:
@@ -1710,9 +1747,13 @@ class FfnBranchMultiFn(torch.autograd.Function):
                     A["gln"] = torch.empty(N, Fd, dtype=x2.dtype, device=x2.device)
                     for i, sg in enumerate(segs):
                         r = slice(sg.row0, sg.end)
-                        hip.ln_geglu_fwd(A["h0"][r], A["h1"][r], P["fln_w@%d" % i], P["fln_b@%d" % i], out=A["gln"][r], want_stats=False)
+                        hip.ln_geglu_fwd(A["h0"][r], A["h1"][r], P["fln_w@%d" % i], P["fln_b@%d" % i], out=A["gln"][r], want_stats=False,
+                                         ps=pss[i] if ctx.zero_rows else None, rows_per_sample=sg.S)
         else:  # recompute (the reference's checkpoint_activations behaviour)
-            _, A = FfnBranchMultiFn._compute(x2, segs, pss, params, True, not ctx.dg_fused, xmap=xmap, listed=kept is None and ctx.dg_fused)
+            info = {}
+            _, A = FfnBranchMultiFn._compute(x2, segs, pss, params, True, not ctx.dg_fused, xmap=xmap, listed=kept is None and ctx.dg_fused,
+                                             info=info)
+            assert info["zero_rows"] == ctx.zero_rows
         if not dout.is_contiguous():
             dout = dout.contiguous()
         dout_full = dout
@@ -1739,12 +1780,18 @@ class FfnBranchMultiFn(torch.autograd.Function):
         # (entries carry the problem index); the fp8 route stays dense
         need_dxln2 = upstream and (need_x or needs["ln2_w"] or needs["ln2_b"])
         wins, dxln2 = None, None
+        ln2_one = nseg == 1 and segs[0].row0 == 0 and segs[0].rows == N
         if upstream and kept is None and not any(sg.pad for sg in segs) and not fp8b:
             dxln2 = torch.empty(N, H, dtype=dt, device=dev) if need_dxln2 else None
+            # (SKIP_ZERO_ROWS) d LN_F(g) is read by op_ln_geglu_bwd alone, which takes its segment's multipliers; d LN2(x) by the
+            # LayerNorm backward over ALL rows, which takes one (ps, S) pair: one segment
+            filled, unread = _bwd_fills([(dgln, has_fln), (dxln2, ln2_one)])
             wins = _dgrad_windows([(pss[i], sg.row0, sg.S, sg.B, 1) for i, sg in enumerate(segs)],
                                   [[(i, 0, sg.row0)] for i, sg in enumerate(segs)] + ([[(i, i, sg.row0) for i, sg in enumerate(segs)]] if need_dxln2 else []),
-                                  [dgln] + ([dxln2] if need_dxln2 else []),
-                                  [(sg.rows, Fd, H) for sg in segs] + ([(sg.rows, H, 2 * Fd) for sg in segs] if need_dxln2 and nseg == 1 else []))
+                                  filled,
+                                  [(sg.rows, Fd, H) for sg in segs] + ([(sg.rows, H, 2 * Fd) for sg in segs] if need_dxln2 and nseg == 1 else []),
+                                  unread=unread)
+        zr_b = SKIP_ZERO_ROWS and wins is not None  # the row kernels of this backward leave out the rows of dropped samples
         for i, sg in enumerate(segs):
             r = slice(sg.row0, sg.end)
             k = lambda n: "%s@%d" % (n, i)  # noqa: E731
@@ -1754,7 +1801,7 @@ class FfnBranchMultiFn(torch.autograd.Function):
                 if P[k("b2")] is not None:
                     pairs.append((P[k("b2")], g0))
             dy2 = _resid_backward(dout_full if mapped else dout[r], A["y2"][r] if A["y2"] is not None else None, P["g2"], pss[i], sg.S,
-                                  "g2", k("b2"), direct, G, needs, g0=g0, rows=xmap[r] if mapped else None, fold=fold)
+                                  "g2", k("b2"), direct, G, needs, g0=g0, rows=xmap[r] if mapped else None, fold=fold, skip_zero_rows=zr_b)
             if fused:  # (the hook rides on the last segment's problem: by then every (bias, g0) pair is listed)
                 weight_grad(k("w2"), dy2, A["gln"][r], side=(P[k("w2")], rd_views[i], P["g2"]),
                             after=_gamma_finish_hook(rowdot, direct["g2"], pairs, True) if i == nseg - 1 else None, ktiles=kts[i])
@@ -1777,7 +1824,8 @@ class FfnBranchMultiFn(torch.autograd.Function):
                 want = needs[k("fln_w")] or needs[k("fln_b")]
                 (tw, tb2), acc = _targets(direct, k("fln_w"), k("fln_b")) if want else ((None, None), False)
                 _, _, dw_, db2_ = hip.ln_geglu_bwd(dgln[r], A["h0"][r], A["h1"][r], P[k("fln_w")], A["mean_f"][r], A["rstd_f"][r], dw=tw,
-                                                   db=tb2, accumulate=acc, need_wgrad=want, dh0=dpart[pair[0]], dh1=dpart[pair[1]])
+                                                   db=tb2, accumulate=acc, need_wgrad=want, dh0=dpart[pair[0]], dh1=dpart[pair[1]],
+                                                   ps=pss[i] if zr_b or ctx.zero_rows else None, rows_per_sample=sg.S)
                 if want:
                     _finish(direct, G, (k("fln_w"), k("fln_b")), (dw_, db2_), acc)
             else:
@@ -1812,7 +1860,8 @@ class FfnBranchMultiFn(torch.autograd.Function):
             want = needs["ln2_w"] or needs["ln2_b"]
             (tw, tb), acc = _targets(direct, "ln2_w", "ln2_b") if want else ((None, None), False)
             dx, dw_, db_ = hip.layernorm_bwd(dxln2, x2, P["ln2_w"], P["ln2_b"], A["mean2"], A["rstd2"], add=dout, dw=tw, db=tb,
-                                             accumulate=acc, need_wgrad=want, dx=torch.empty_like(dout_full) if mapped else None, x_rows=xmap)
+                                             accumulate=acc, need_wgrad=want, dx=torch.empty_like(dout_full) if mapped else None, x_rows=xmap,
+                                             ps=pss[0] if zr_b and ln2_one else None, rows_per_sample=segs[0].S)
             if want:
                 _finish(direct, G, ("ln2_w", "ln2_b"), (dw_, db_), acc)
         if dx is None and need_x:
