@@ -577,6 +577,42 @@ int op_image_resize_normalize_flip(const void* src, int64_t src_bytes, const int
 int op_mix_images(const void* x, void* out, int in_dtype, int out_dtype, int64_t B, int64_t CHW, int64_t H, int64_t W, const int* kind,
                   const float* lam, const float* one_minus_lam, const int* box, void* stream);
 
+/* ---- photometric train transforms on the resized uint8 batch: ColorJitter, GaussianBlur, ToTensor / Normalize (csrc/photometric.hip) ----
+ * The steps of the reference's train transforms between the resize and ToTensor, on img = dense uint8 [B, S, S, 3] on the device (what
+ * op_image_resize_normalize* writes with out_dtype 2), bit for bit PIL.  Additive: op_abi_version() stays 10, no existing entry point
+ * changed.  All three: 16 <= S <= 1024, S % 16 == 0, 0 <= B <= 65535, img 16-byte aligned; else OP_EINVAL before anything is launched.
+ * B == 0 returns without a launch.
+ *
+ * op_image_color_jitter, in place: RandomDistortion = torchvision ColorJitter through PIL.ImageEnhance (utils/transforms.py:144-157;
+ * data/vl_data/nlvr2_dataset.py:35, data/vision_data/image_classify_dataset.py:57).  ops int32 [B, 3] (0 none, 1 brightness, 2 contrast,
+ * 3 saturation), applied in order, and factor fp32 [B, 3] are DEVICE tables; ops_host / factor_host the same tables in HOST memory
+ * (validated here, decide the launches).  Every op is Image.blend(degenerate, image, f) per byte:
+ *   t = fadd_rn((float)d, fmul_rn(f, (float)(p - d))) -- two rounded fp32 operations, never an fma -- then clipped to 0 ... 255 and truncated
+ * with d = 0 (brightness), L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 of the pixel (saturation), or the image's
+ * m = (2 sum(L) + S S) / (2 S S) as it is when the contrast op runs (contrast).  sums: DEVICE uint32 [B] workspace, zeroed and filled here.
+ * One launch sums L for the images with a contrast op (integer atomics: two runs give the same bits; skipped when no image has one), one
+ * applies the chain; an image whose three ops are 0 is neither read nor written, and a batch of such images launches nothing.
+ * OP_EINVAL: an op outside 0 ... 3, more than one contrast op in an image, a negative or non-finite factor, null or misaligned tables.
+ *
+ * op_image_gaussian_blur, in place: ImageFilter.GaussianBlur (utils/transforms.py:160-188; data/vl_data/refcoco_dataset.py:33,
+ * nlvr2_dataset.py:36, image_classify_dataset.py:58): three extended box blurs along x, then three along y, each
+ *   out[x] = (acc ww + far fw + 2^23) >> 24 in 32-bit unsigned arithmetic, acc = sum of in[clamp(x + i)] for |i| <= R,
+ *   far = in[clamp(x - R - 1)] + in[clamp(x + R + 1)].
+ * R int32 [B], ww / fw uint32 [B] (one-peace_amd/imageprep.py: gaussian_box_params) and on uint8 [B] are DEVICE tables, R_host / on_host
+ * HOST copies.  Images with on == 0 are not touched; a batch of them launches nothing.  Two launches: rows, then columns, each staging what
+ * it overwrites in LDS first.  OP_EINVAL: R outside 0 ... 32 for an image with on != 0, null or misaligned tables.
+ *
+ * op_image_normalize_flip: ToTensor, Normalize and RandomHorizontalFlip (image_classify_dataset.py:59-63, nlvr2_dataset.py:37-41,
+ * refcoco_dataset.py:34-35) of src uint8 [B, S, S, 3] into out [B, 3, S, S] bf16 (out_dtype 0) or f32 (1): the arithmetic, the cast and the
+ * flip flags (flip uint8 [B] on the DEVICE or NULL) of op_image_resize_normalize_flip -- one device function serves both.  mean, stdev: HOST
+ * float[3].  out 16-byte aligned and not overlapping src. */
+int op_image_color_jitter(void* img, int64_t B, int64_t S, const int* ops, const float* factor, const int* ops_host,
+                          const float* factor_host, unsigned* sums, void* stream);
+int op_image_gaussian_blur(void* img, int64_t B, int64_t S, const int* R, const unsigned* ww, const unsigned* fw, const uint8_t* on,
+                           const int* R_host, const uint8_t* on_host, void* stream);
+int op_image_normalize_flip(const void* src, int64_t B, int64_t S, const float* mean, const float* stdev, void* out, int out_dtype,
+                            const uint8_t* flip, void* stream);
+
 /* ---- audio pre-processing: channel mean + whole-clip layer norm + crop / tile / pad (csrc/audioprep.hip) -----------------------
  * Replaces the host loop of one_peace/models/one_peace/hub_interface.py:170-193 and data/base_dataset.py:84-102 (audio_postprocess:
  * feats.mean(-1), F.layer_norm(feats, feats.shape) over the WHOLE clip, crop to max_len samples from the start, repeat the normalised

@@ -11,8 +11,13 @@ and the two kernels of csrc/image.hip on a device, PIL itself on the CPU.
 (``params``), the pixels are mixed by ops.mix_images (op_mix_images, csrc/augment.hip: one pass, in place) and the soft targets built
 by ops.mix_targets; they are what ops.classify_loss takes on its soft route.
 
-Not provided (out of scope): RandAugment, RandomDistortion / ColorJitter, GaussianBlur, RandomErasing, timm's create_transform, the
-RefCOCO box transforms and BPE tokenisation."""
+``ColorJitter`` (the reference's ``RandomDistortion``, utils/transforms.py:144-157) and ``GaussianBlur`` (utils/transforms.py:160-188) draw
+the per-image tables of the photometric steps; ops.preprocess_images runs them between the resize and ToTensor (csrc/photometric.hip on
+a device, PIL on the CPU).  ``GroundingTransform`` is the RefCOCO train transform with its box arithmetic
+(data/vl_data/refcoco_dataset.py:31-36).
+
+Not provided (out of scope): RandAugment (the reference's utils/randaugment.py is defined by OpenCV's warpAffine / filter2D), RandomErasing,
+timm's create_transform, hue jitter (every use in the reference passes hue = 0), polygon targets and BPE tokenisation."""
 import numpy as np
 import torch
 
@@ -24,10 +29,11 @@ class TrainImageTransform:
 
     min_scale: RandomResizedCrop(size, scale=(min_scale, 1.0), ratio=(3/4, 4/3), BICUBIC); with min_scale=0.9 this is the pretraining
     transform.  center_crop: Resize(size) + CenterCrop(size) (exclusive with min_scale).  Neither: Resize((size, size)).
-    hflip: probability of RandomHorizontalFlip, applied last.  generator: the torch.Generator of the crop boxes and flips (None:
+    hflip: probability of RandomHorizontalFlip, applied last.  color_jitter / blur: a ColorJitter / GaussianBlur of this module, applied
+    to the resized uint8 image in that order, before the flip (the reference's Compose order); None: the step is absent.  generator: the torch.Generator of the crop boxes and flips (None:
     torch's global one).  The random stream is torch's, not torchvision's: see imageprep.random_resized_crop_params."""
 
-    def __init__(self, size, min_scale=None, center_crop=False, hflip=0.0, generator=None):
+    def __init__(self, size, min_scale=None, center_crop=False, hflip=0.0, generator=None, color_jitter=None, blur=None):
         imageprep.check_size(size)
         if min_scale is not None and center_crop:
             raise ValueError("TrainImageTransform: min_scale (RandomResizedCrop) and center_crop are mutually exclusive")
@@ -36,6 +42,7 @@ class TrainImageTransform:
         if not 0.0 <= hflip <= 1.0:
             raise ValueError("TrainImageTransform: hflip is a probability, got %r" % (hflip,))
         self.size, self.min_scale, self.center_crop, self.hflip, self.generator = size, min_scale, center_crop, hflip, generator
+        self.color_jitter, self.blur = color_jitter, blur
 
     def params(self, sizes):
         """(crops or None, flips or None) for images of the given (height, width)."""
@@ -50,7 +57,127 @@ class TrainImageTransform:
         images = list(images)
         sizes = [(im.size[1], im.size[0]) if ops._is_pil(im) else tuple(im.shape[:2]) for im in images]
         crops, flips = self.params(sizes)
-        return ops.preprocess_images(images, self.size, mean, std, dtype, device, crops=crops, center_crop=self.center_crop, flips=flips)
+        if self.color_jitter is None and self.blur is None:
+            return ops.preprocess_images(images, self.size, mean, std, dtype, device, crops=crops, center_crop=self.center_crop, flips=flips)
+        jitter = None if self.color_jitter is None else self.color_jitter.params(len(images))
+        blur = None if self.blur is None else self.blur.params(len(images))
+        return ops.preprocess_images(images, self.size, mean, std, dtype, device, crops=crops, center_crop=self.center_crop, flips=flips,
+                                     jitter=jitter, blur=blur)
+
+
+def _jitter_range(value, name):
+    """torchvision's ColorJitter._check_input for brightness / contrast / saturation: a number v >= 0 is [max(0, 1 - v), 1 + v], a pair is
+    taken as it is; None when the range is [1, 1] (the op is skipped)."""
+    if isinstance(value, (int, float)):
+        if value < 0:
+            raise ValueError("ColorJitter: %s must be non-negative, got %r" % (name, value))
+        lo, hi = max(0.0, 1.0 - float(value)), 1.0 + float(value)
+    else:
+        lo, hi = (float(v) for v in value)
+        if not 0.0 <= lo <= hi or hi == float("inf"):
+            raise ValueError("ColorJitter: %s range must be 0 <= min <= max < inf, got %r" % (name, value))
+    return None if lo == hi == 1.0 else (lo, hi)
+
+
+class ColorJitter:
+    """torchvision's ColorJitter(brightness, contrast, saturation) applied with probability `prob`: the reference's
+    RandomDistortion(b, c, s, 0, prob) (utils/transforms.py:144-157) is ColorJitter(b, c, s, prob=prob); NLVR2 and the raw_transform of the
+    image classification use RandomDistortion(0.4, 0.4, 0.4, 0, 0.5) = ColorJitter(0.4, 0.4, 0.4, prob=0.5).
+
+    Per image: a permutation of (brightness, contrast, saturation, hue) gives the order of the ops, each factor is uniform in
+    [max(0, 1 - v), 1 + v]; an op whose v is 0 is skipped.  hue != 0 raises NotImplementedError (not provided; the reference passes 0).
+    The draws use torch's random stream (`generator`); it is NOT claimed equal to torchvision's, only the procedure is restated."""
+
+    def __init__(self, brightness=0, contrast=0, saturation=0, hue=0, prob=1.0, generator=None):
+        if (hue != 0) if isinstance(hue, (int, float)) else (tuple(hue) != (0, 0)):
+            raise NotImplementedError("ColorJitter: hue jitter is not provided (every use in the reference passes hue = 0)")
+        if not 0.0 <= prob <= 1.0:
+            raise ValueError("ColorJitter: prob is a probability, got %r" % (prob,))
+        self.ranges = {1: _jitter_range(brightness, "brightness"), 2: _jitter_range(contrast, "contrast"),
+                       3: _jitter_range(saturation, "saturation")}
+        self.prob, self.generator = prob, generator
+
+    def params(self, B):
+        """(ops int32 [B, 3], factors float32 [B, 3]): the tables of ops.color_jitter / ops.preprocess_images(jitter = ...)."""
+        chains = []
+        for _ in range(B):
+            chain = []
+            if float(torch.rand(1, generator=self.generator)) < self.prob:
+                for fn in torch.randperm(4, generator=self.generator).tolist():  # 0 brightness, 1 contrast, 2 saturation, 3 hue
+                    rng = self.ranges.get(fn + 1)
+                    if rng is not None:
+                        chain.append((fn + 1, float(torch.empty(1).uniform_(rng[0], rng[1], generator=self.generator))))
+            chains.append(chain)
+        return imageprep.jitter_table(chains)
+
+
+class GaussianBlur:
+    """The reference's GaussianBlur(p, radius_min, radius_max) (utils/transforms.py:160-188): with a draw u ~ U[0, 1), the image is blurred
+    when u <= p, by ImageFilter.GaussianBlur(radius ~ U(radius_min, radius_max)).  torch's random stream (`generator`)."""
+
+    def __init__(self, p=0.5, radius_min=0.1, radius_max=2.0, generator=None):
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("GaussianBlur: p is a probability, got %r" % (p,))
+        if not 0.0 < radius_min <= radius_max:
+            raise ValueError("GaussianBlur: need 0 < radius_min <= radius_max, got %r, %r" % (radius_min, radius_max))
+        imageprep.gaussian_box_params(radius_max)  # (a ValueError when the device kernel cannot take the largest radius)
+        self.prob, self.radius_min, self.radius_max, self.generator = p, radius_min, radius_max, generator
+
+    def params(self, B):
+        """One entry per image: the radius, or None for an image that is not blurred (ops.gaussian_blur's `radii`)."""
+        radii = []
+        for _ in range(B):
+            do_it = float(torch.rand(1, generator=self.generator)) <= self.prob
+            radii.append(float(torch.empty(1).uniform_(self.radius_min, self.radius_max, generator=self.generator)) if do_it else None)
+        return radii
+
+
+class GroundingTransform:
+    """The RefCOCO train transform (data/vl_data/refcoco_dataset.py:31-36): RandomResize([size], max_size=size), GaussianBlur, ToTensor and
+    Normalize(max_image_size=size) with the box arithmetic of utils/transforms.py (resize: 53-60, Normalize: 113-116).
+
+    The resize is always to (size, size): get_size_with_aspect_ratio(image_size, size, max_size=size) puts the shorter side at `size` and
+    the longer at int(size * long / short) >= size, then clips both to max_size = size (``resized_size``; the early exit for a shorter
+    side that already equals `size` clips the same way).  So the aspect ratio is not kept and the ratios are rw = float(size) / float(w),
+    rh = float(size) / float(h).  Boxes (x0, y0, x1, y1 in pixels) become boxes * fp32[rw, rh, rw, rh] / size, in torch's fp32 arithmetic
+    as the reference runs it; target["size"] = [size, size].  blur: a GaussianBlur of this module or None.  Polygons are not handled (the
+    dataset never passes them)."""
+
+    def __init__(self, size, blur=None):
+        imageprep.check_size(size)
+        self.size, self.blur = size, blur
+
+    @staticmethod
+    def resized_size(w, h, size, max_size=None):
+        """(oh, ow) of the reference's get_size_with_aspect_ratio((w, h), size, max_size), restated."""
+        if (w <= h and w == size) or (h <= w and h == size):
+            if max_size is not None:
+                h, w = min(h, int(max_size)), min(w, int(max_size))
+            return h, w
+        if w < h:
+            ow, oh = size, int(size * h / w)
+        else:
+            oh, ow = size, int(size * w / h)
+        if max_size is not None:
+            oh, ow = min(oh, int(max_size)), min(ow, int(max_size))
+        return oh, ow
+
+    def boxes(self, boxes, w, h):
+        """fp32 boxes of a w x h image after the resize to (size, size) and Normalize's division by max_image_size = size."""
+        ratio_width, ratio_height = float(self.size) / float(w), float(self.size) / float(h)
+        scaled = torch.as_tensor(boxes, dtype=torch.float32) * torch.as_tensor([ratio_width, ratio_height, ratio_width, ratio_height])
+        return scaled / self.size
+
+    def __call__(self, images, boxes, dtype=torch.float32, device="cpu", mean=None, std=None):
+        """(x [B, 3, size, size] on `device`, targets): boxes[i] = the [n_i, 4] (or [4]) boxes of image i in pixels; targets[i] =
+        {"boxes": fp32 of the same shape on the CPU, "size": tensor([size, size])}."""
+        images = list(images)
+        if len(boxes) != len(images):
+            raise ValueError("GroundingTransform: need the boxes of every image, got %d for %d images" % (len(boxes), len(images)))
+        sizes = [(im.size[1], im.size[0]) if ops._is_pil(im) else tuple(im.shape[:2]) for im in images]
+        targets = [{"boxes": self.boxes(b, w, h), "size": torch.tensor([self.size, self.size])} for b, (h, w) in zip(boxes, sizes)]
+        blur = None if self.blur is None else self.blur.params(len(images))
+        return ops.preprocess_images(images, self.size, mean, std, dtype, device, blur=blur), targets
 
 
 class Mixup:

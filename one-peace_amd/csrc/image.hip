@@ -22,6 +22,7 @@
 // shifted / windowed coefficient records built on the host, and RandomHorizontalFlip (image_classify_dataset.py:59, nlvr2_dataset.py:37) is a
 // per-image flag under which the vertical kernel stores its 4-column group mirrored.
 #include "common.h"
+#include "image_store.h"
 
 #include <algorithm>
 
@@ -34,7 +35,6 @@ constexpr int IR_DESC = 11;    // int64 per image: src_off, H, W, cx_off, kx, cy
 constexpr int IR_PREC = 22;
 constexpr int IR_MAX_S = 1024;
 constexpr int IR_SLACK = 16;
-constexpr int IR_OUT_U8 = 2;
 
 __device__ __forceinline__ int ir_clip8(int acc) { return min(max(acc >> IR_PREC, 0), 255); }
 
@@ -126,8 +126,6 @@ __global__ __launch_bounds__(IR_THREADS) void ir_horizontal_kernel(const uint8_t
   }
 }
 
-struct IrNorm { float mean[3], stdev[3]; };
-
 template <int OUT>
 __global__ __launch_bounds__(IR_THREADS) void ir_vertical_kernel(const uint8_t* __restrict__ tmp, const int64_t* __restrict__ desc,
                                                                  const int* __restrict__ coef, void* __restrict__ out, int S, IrNorm nm,
@@ -190,37 +188,7 @@ __global__ __launch_bounds__(IR_THREADS) void ir_vertical_kernel(const uint8_t* 
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) u[x][ch] = ir_clip8(acc[x][ch]);
       }
-    // a flipped image writes column S - 1 - x: the 4-column group goes to group G - 1 - g with its columns reversed (same vector stores)
-    const int go = flipped ? G - 1 - g : g;
-    if (flipped) {
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const int a = u[0][ch], b = u[1][ch];
-        u[0][ch] = u[3][ch], u[1][ch] = u[2][ch], u[2][ch] = b, u[3][ch] = a;
-      }
-    }
-    if constexpr (OUT == IR_OUT_U8) {
-      unsigned* q = reinterpret_cast<unsigned*>(reinterpret_cast<uint8_t*>(out) + (((int64_t)img * S + y) * S + go * 4) * 3);
-      q[0] = (unsigned)u[0][0] | (unsigned)u[0][1] << 8 | (unsigned)u[0][2] << 16 | (unsigned)u[1][0] << 24;
-      q[1] = (unsigned)u[1][1] | (unsigned)u[1][2] << 8 | (unsigned)u[2][0] << 16 | (unsigned)u[2][1] << 24;
-      q[2] = (unsigned)u[2][2] | (unsigned)u[3][0] << 8 | (unsigned)u[3][1] << 16 | (unsigned)u[3][2] << 24;
-    } else {
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        float v[4];
-#pragma unroll
-        for (int x = 0; x < 4; ++x) v[x] = ((float)u[x][ch] / 255.0f - nm.mean[ch]) / nm.stdev[ch];  // torchvision's order, IEEE
-        const int64_t e = (((int64_t)img * 3 + ch) * S + y) * S + go * 4;
-        if constexpr (OUT == OP_DT_BF16) {
-          bf16x4 r;
-#pragma unroll
-          for (int x = 0; x < 4; ++x) r[x] = (bf16_t)v[x];
-          *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(out) + e) = r;
-        } else {
-          *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out) + e) = (f32x4){v[0], v[1], v[2], v[3]};
-        }
-      }
-    }
+    ir_store_group<OUT>(out, u, img, y, g, G, S, nm, flipped);
   }
 }
 

@@ -106,6 +106,9 @@ SIGNATURES = {
     "op_image_resize_normalize": (c_int, [P, I64, P, P, I64, P, I64, I64, P, P, P, c_int, P, I64, P]),
     "op_image_resize_normalize_flip": (c_int, [P, I64, P, P, I64, P, I64, I64, P, P, P, c_int, P, I64, P, P]),
     "op_mix_images": (c_int, [P, P, c_int, c_int, I64, I64, I64, I64, P, P, P, P, P]),
+    "op_image_color_jitter": (c_int, [P, I64, I64, P, P, P, P, P, P]),
+    "op_image_gaussian_blur": (c_int, [P, I64, I64, P, P, P, P, P, P, P]),
+    "op_image_normalize_flip": (c_int, [P, I64, I64, P, P, P, c_int, P, P]),
     "op_audio_normalize_pad": (c_int, [P, I64, P, P, I64, I64, I64, P, I64, c_int, P, I64, P]),
     "op_audio_resample": (c_int, [P, I64, P, P, I64, P, I64, P, I64, P]),
     "op_average_precision_workspace_bytes": (I64, [I64, I64]),
@@ -1428,6 +1431,76 @@ def mix_images(x, params, out=None):
     if rc == ENOTSUP:
         return None
     _check(rc, "op_mix_images")
+    return out
+
+
+def _u8_batch(u8, what):
+    """(B, S) of a dense uint8 [B, S, S, 3] CUDA batch."""
+    _req(u8, "u8", torch.uint8)
+    if u8.dim() != 4 or u8.shape[3] != 3 or u8.shape[1] != u8.shape[2]:
+        raise ValueError("%s: need uint8 [B, S, S, 3], got %s" % (what, tuple(u8.shape)))
+    return u8.shape[0], u8.shape[1]
+
+
+def image_color_jitter(u8, ops, factors):
+    """op_image_color_jitter IN PLACE on u8 [B, S, S, 3] (uint8, contiguous, CUDA): per image the chain ops int32 [B, 3] (0 none, 1 brightness,
+    2 contrast, 3 saturation) with factors fp32 [B, 3] (host arrays, imageprep.jitter_table), PIL.ImageEnhance bit for bit.  The tables
+    and the zeroed sum(L) workspace go to the device as ONE 28 x B-byte buffer.  Returns u8."""
+    import numpy as np
+    B, S = _u8_batch(u8, "image_color_jitter")
+    ops = np.ascontiguousarray(np.asarray(ops, dtype=np.int32).reshape(B, 3))
+    fac = np.ascontiguousarray(np.asarray(factors, dtype=np.float32).reshape(B, 3))
+    if B == 0:
+        return u8
+    host = np.zeros(7 * B, dtype=np.int32)
+    host[:3 * B], host[3 * B:6 * B] = ops.reshape(-1), fac.view(np.int32).reshape(-1)
+    with torch.cuda.device(u8.device):
+        dev = torch.from_numpy(host).to(u8.device)
+        base = dev.data_ptr()
+        _check(lib().op_image_color_jitter(ptr(u8), B, S, c_void_p(base), c_void_p(base + 12 * B), ops.ctypes.data_as(c_void_p),
+                                           fac.ctypes.data_as(c_void_p), c_void_p(base + 24 * B), stream()), "op_image_color_jitter")
+    return u8
+
+
+def image_gaussian_blur(u8, R, ww, fw, on):
+    """op_image_gaussian_blur IN PLACE on u8 [B, S, S, 3] (uint8, contiguous, CUDA): ImageFilter.GaussianBlur bit for bit, with the per-image
+    box parameters R, ww, fw (imageprep.gaussian_box_params) and on flags (0 = not blurred, not touched), host arrays of B entries; they go
+    to the device as ONE 16 x B-byte buffer.  Returns u8."""
+    import numpy as np
+    B, S = _u8_batch(u8, "image_gaussian_blur")
+    R = np.ascontiguousarray(np.asarray(R, dtype=np.int32).reshape(B))
+    on = np.ascontiguousarray(np.asarray(on, dtype=np.uint8).reshape(B))
+    if B == 0:
+        return u8
+    host = np.zeros(4 * B, dtype=np.uint32)
+    host[:B], host[B:2 * B], host[2 * B:3 * B] = R.view(np.uint32), np.asarray(ww, dtype=np.uint32).reshape(B), np.asarray(fw, dtype=np.uint32).reshape(B)
+    host[3 * B:].view(np.uint8)[:B] = on
+    with torch.cuda.device(u8.device):
+        dev = torch.from_numpy(host.view(np.int32)).to(u8.device)
+        base = dev.data_ptr()
+        _check(lib().op_image_gaussian_blur(ptr(u8), B, S, c_void_p(base), c_void_p(base + 4 * B), c_void_p(base + 8 * B), c_void_p(base + 12 * B),
+                                            R.ctypes.data_as(c_void_p), on.ctypes.data_as(c_void_p), stream()), "op_image_gaussian_blur")
+    return u8
+
+
+def image_normalize_flip(u8, mean, std, dtype=torch.float32, flips=None):
+    """[B, 3, S, S] bf16 / fp32 from u8 [B, S, S, 3] (uint8, contiguous, CUDA): op_image_normalize_flip, the ToTensor / Normalize arithmetic, the
+    cast and the flip of op_image_resize_normalize_flip.  flips: None, or one flag per image (a uint8 CUDA tensor, or host values)."""
+    B, S = _u8_batch(u8, "image_normalize_flip")
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("image_normalize_flip: dtype must be bfloat16 or float32, got %s" % dtype)
+    out = torch.empty((B, 3, S, S), dtype=dtype, device=u8.device)
+    if B == 0:
+        return out
+    with torch.cuda.device(u8.device):
+        if flips is not None and not (torch.is_tensor(flips) and flips.is_cuda):
+            flips = torch.as_tensor([1 if f else 0 for f in (flips.tolist() if hasattr(flips, "tolist") else flips)], dtype=torch.uint8).to(u8.device)
+        if flips is not None:
+            _req(flips, "flips", torch.uint8)
+            if flips.numel() != B:
+                raise ValueError("image_normalize_flip: need one flip flag per image, got %d for %d images" % (flips.numel(), B))
+        _check(lib().op_image_normalize_flip(ptr(u8), B, S, (c_float * 3)(*mean), (c_float * 3)(*std), ptr(out), _IMAGE_OUT[dtype], ptr(flips),
+                                             stream()), "op_image_normalize_flip")
     return out
 
 

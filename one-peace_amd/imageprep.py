@@ -293,6 +293,85 @@ def apply_packed(packed):
     return out
 
 
+# ---- photometric train transforms: the host-side tables of op_image_color_jitter / op_image_gaussian_blur (csrc/photometric.hip) ----
+JITTER_OPS = {"none": 0, "brightness": 1, "contrast": 2, "saturation": 3}  # op codes of the ops table (include/onepeace_hip.h)
+MAX_BOX_RADIUS = 32  # op_image_gaussian_blur: integer box radius R <= 32 (GaussianBlur radii up to ~33)
+
+
+def jitter_table(chains):
+    """(ops int32 [B, 3], factors float32 [B, 3]) from one chain per image: None / () for an untouched image, else up to three
+    (op, factor) pairs in the order they are applied, op a name or code of JITTER_OPS.  Unused slots are (0, 1.0).  ValueError: an unknown
+    op, more than three ops or more than one contrast op in an image (torchvision's ColorJitter applies each at most once), a factor that
+    is negative or not finite."""
+    chains = list(chains)
+    ops = np.zeros((len(chains), 3), dtype=np.int32)
+    factors = np.ones((len(chains), 3), dtype=np.float32)
+    for i, chain in enumerate(chains):
+        chain = [] if chain is None else list(chain)
+        if len(chain) > 3:
+            raise ValueError("jitter_table: image %d has %d ops, at most 3" % (i, len(chain)))
+        for k, (op, f) in enumerate(chain):
+            code = JITTER_OPS.get(op) if isinstance(op, str) else (int(op) if int(op) in JITTER_OPS.values() else None)
+            if code is None:
+                raise ValueError("jitter_table: image %d: unknown op %r (need one of %s or 0 ... 3)" % (i, op, sorted(JITTER_OPS)))
+            f = float(f)
+            if not math.isfinite(f) or f < 0.0 or f > float(np.finfo(np.float32).max):  # (finite as fp32, too)
+                raise ValueError("jitter_table: image %d: factor %r must be finite and >= 0" % (i, f))
+            ops[i, k], factors[i, k] = code, f
+        if int((ops[i] == JITTER_OPS["contrast"]).sum()) > 1:
+            raise ValueError("jitter_table: image %d has more than one contrast op" % i)
+    return ops, factors
+
+
+def check_jitter(jitter, count):
+    """The (ops, factors) tables of `count` images as (int32 [count, 3], float32 [count, 3]), validated as jitter_table validates."""
+    ops, factors = jitter
+    ops = np.asarray(ops.cpu() if torch.is_tensor(ops) else ops)
+    factors = np.asarray(factors.cpu() if torch.is_tensor(factors) else factors)
+    if ops.size != 3 * count or factors.size != 3 * count:
+        raise ValueError("jitter: need ops and factors of [%d, 3], got %s and %s" % (count, ops.shape, factors.shape))
+    ops, factors = ops.reshape(count, 3), factors.reshape(count, 3)
+    return jitter_table([list(zip(o.tolist(), f.tolist())) for o, f in zip(ops, factors)])
+
+
+def gaussian_box_params(radius):
+    """(R, ww, fw) of the three extended box blurs per axis that PIL's ImageFilter.GaussianBlur(radius) runs (src/libImaging/BoxBlur.c):
+    with C-float s2 = fl32(fl32(r r) / 3), then in doubles L = sqrt(12 s2 + 1), l = floor((L - 1) / 2),
+    a = (2 l + 1)(l (l + 1) - 3 s2) / (6 (s2 - (l + 1)^2)) and fr = fl32(l + a); a line pass uses R = (int)fr, ww = (uint32)(2^24 / (2 fr + 1))
+    in fp32 and fw = (2^24 - (2 R + 1) ww) / 2.  ValueError: a radius that is not positive and finite, or R > MAX_BOX_RADIUS."""
+    r = float(radius)
+    if not math.isfinite(r) or r <= 0.0:
+        raise ValueError("gaussian_box_params: radius must be positive and finite, got %r" % (radius,))
+    r = np.float32(r)
+    s2 = float(np.float32(np.float32(r * r) / np.float32(3)))
+    L = math.sqrt(12.0 * s2 + 1.0)
+    l = math.floor((L - 1.0) / 2.0)
+    a = (2 * l + 1) * (l * (l + 1) - 3 * s2) / (6 * (s2 - (l + 1) * (l + 1)))
+    fr = np.float32(l + a)
+    R = int(fr)
+    if R > MAX_BOX_RADIUS:
+        raise ValueError("gaussian_box_params: radius %r gives a box radius of %d, at most %d" % (radius, R, MAX_BOX_RADIUS))
+    ww = int(np.float32(1 << 24) / np.float32(np.float32(2) * fr + np.float32(1)))
+    fw = ((1 << 24) - (2 * R + 1) * ww) // 2
+    return R, ww, fw
+
+
+def blur_table(radii):
+    """(R int32 [B], ww uint32 [B], fw uint32 [B], on uint8 [B]) from one radius per image; None or a radius <= 0 means not blurred."""
+    radii = list(radii.tolist() if hasattr(radii, "tolist") else radii)
+    B = len(radii)
+    R, ww, fw, on = np.zeros(B, np.int32), np.zeros(B, np.uint32), np.zeros(B, np.uint32), np.zeros(B, np.uint8)
+    for i, r in enumerate(radii):
+        if r is None:
+            continue
+        if math.isnan(float(r)):
+            raise ValueError("blur_table: radius %d is NaN" % i)
+        if r > 0:
+            R[i], ww[i], fw[i] = gaussian_box_params(r)
+            on[i] = 1
+    return R, ww, fw, on
+
+
 def random_resized_crop_params(height, width, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), generator=None):
     """(top, left, h, w) of torchvision's RandomResizedCrop.get_params for a height x width image, restated with torch's RNG
     (`generator`): up to 10 tries of area * U(scale), exp(U(log ratio)), w = int(round(sqrt(a r))), h = int(round(sqrt(a / r))), the

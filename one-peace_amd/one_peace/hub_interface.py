@@ -128,9 +128,10 @@ class OnePeaceHubInterface:
         normalisation run in op_image_resize_normalize (bit-identical to PIL + torchvision); on the CPU PIL does the resize.
         A floating-point tensor is taken as already pre-processed and only moved and cast, as before.
         The training transforms (RandomResizedCrop, Resize + CenterCrop, RandomHorizontalFlip) and Mixup / CutMix are
-        augment.TrainImageTransform and augment.Mixup, on the same kernels.
-        Out of scope: JPEG / PNG decoding stays in PIL on the host; BPE for process_text, RandAugment, RandomDistortion / ColorJitter,
-        GaussianBlur and RandomErasing are not provided."""
+        augment.TrainImageTransform and augment.Mixup, on the same kernels; RandomDistortion / ColorJitter and GaussianBlur are
+        augment.ColorJitter and augment.GaussianBlur (csrc/photometric.hip), the RefCOCO transform augment.GroundingTransform.
+        Out of scope: JPEG / PNG decoding stays in PIL on the host; BPE for process_text, RandAugment, RandomErasing, timm's
+        create_transform and hue jitter are not provided."""
         from .. import ops
         if torch.is_tensor(image_list) or isinstance(image_list, np.ndarray):
             batch = torch.as_tensor(image_list)

@@ -681,7 +681,8 @@ def _is_pil(im):
     return type(im).__module__.startswith("PIL.") and hasattr(im, "convert")
 
 
-def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, device="cpu", crops=None, center_crop=False, flips=None):
+def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, device="cpu", crops=None, center_crop=False, flips=None,
+                      jitter=None, blur=None):
     """[B, 3, size, size] in `dtype` on `device` from decoded RGB images (uint8 [H, W, 3] arrays / tensors or PIL images of any
     size): PIL's Image.resize((size, size), BICUBIC), ToTensor and Normalize (CLIP mean / std by default) in torchvision's fp32
     order, then the cast -- the reference's transform, bit for bit.  On a CUDA device this is op_image_resize_normalize
@@ -693,7 +694,14 @@ def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, de
     the image.  center_crop=True: torchvision's Resize(size) + CenterCrop(size) (shorter side to size, the longer to
     int(size * long / short), window at int(round((n - size) / 2.0))); exclusive with crops.  flips: one bool per image,
     RandomHorizontalFlip, applied last as in the reference's Compose.  A box outside its image or with h or w < 1 is a ValueError
-    before anything is copied."""
+    before anything is copied.
+
+    The photometric steps of the train transforms sit between the resize and ToTensor.  jitter: the (ops, factors) tables of
+    color_jitter (RandomDistortion / ColorJitter; augment.ColorJitter.params draws them); blur: one GaussianBlur radius per image, None
+    or <= 0 for an image that is not blurred (augment.GaussianBlur.params).  With either, the device route is the resize to uint8
+    [B, size, size, 3], op_image_color_jitter, op_image_gaussian_blur and op_image_normalize_flip with the flips; the CPU route is the same
+    chain in PIL, in the reference's Compose order (resize, distortion, blur, flip).  With both None the path and the results are those
+    of the plain resize."""
     import numpy as np
 
     from . import imageprep
@@ -708,11 +716,27 @@ def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, de
         crops = imageprep.check_crops(crops, hw)
     if flips is not None:
         flips = imageprep.check_flips(flips, len(images))
+    photometric = jitter is not None or blur is not None
+    if jitter is not None:
+        jitter = imageprep.check_jitter(jitter, len(images))
+    if blur is not None:
+        blur_radii = list(blur.tolist() if hasattr(blur, "tolist") else blur)
+        blur = imageprep.blur_table(blur_radii)  # (validates; the device route's tables)
+        if len(blur[0]) != len(images):
+            raise ValueError("blur: need one radius per image, got %d for %d images" % (len(blur[0]), len(images)))
     dev = torch.device(device)
     if dev.type == "cuda":
         arrs = [np.asarray(im.convert("RGB")) if _is_pil(im) else im for im in images]
-        packed = imageprep.pack_images(arrs, size, crops=crops, center_crop=center_crop, flips=flips)
         kdt = dtype if dtype in (torch.bfloat16, torch.float32) else torch.float32
+        if photometric:
+            packed = imageprep.pack_images(arrs, size, crops=crops, center_crop=center_crop)
+            u8 = hip.image_resize_normalize(packed, dtype=torch.uint8, device=dev)
+            if jitter is not None:
+                hip.image_color_jitter(u8, *jitter)
+            if blur is not None:
+                hip.image_gaussian_blur(u8, *blur)
+            return hip.image_normalize_flip(u8, mean, std, kdt, flips).to(dtype)
+        packed = imageprep.pack_images(arrs, size, crops=crops, center_crop=center_crop, flips=flips)
         return hip.image_resize_normalize(packed, mean, std, kdt, dev).to(dtype)
     from PIL import Image
     out = []
@@ -726,11 +750,104 @@ def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, de
             im = im.resize((new_w, new_h), Image.BICUBIC).crop((left, top, left + size, top + size))
         else:
             im = im.resize((size, size), Image.BICUBIC)
+        if jitter is not None:
+            im = _pil_jitter(im, jitter[0][i], jitter[1][i])
+        if blur is not None and blur[3][i]:
+            im = _pil_blur(im, blur_radii[i])
         if flips is not None and flips[i]:
             im = im.transpose(Image.FLIP_LEFT_RIGHT)
         u8 = torch.from_numpy(np.array(im, dtype=np.uint8))
         out.append(imageprep.to_tensor_normalize(u8, mean, std))
     return torch.stack(out).to(device=dev, dtype=dtype) if out else torch.empty(0, 3, size, size, dtype=dtype, device=dev)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# photometric train transforms on the resized uint8 batch: RandomDistortion / ColorJitter (utils/transforms.py:144-157) and GaussianBlur
+# (utils/transforms.py:160-188), then ToTensor / Normalize / flip
+# --------------------------------------------------------------------------------------------------------------
+def _pil_jitter(im, ops, factors):
+    """torchvision's ColorJitter steps on a PIL image: ImageEnhance.Brightness / Contrast / Color in the order of `ops`."""
+    from PIL import ImageEnhance
+    enhancers = {1: ImageEnhance.Brightness, 2: ImageEnhance.Contrast, 3: ImageEnhance.Color}
+    for op, f in zip(ops, factors):
+        if int(op) != 0:
+            im = enhancers[int(op)](im).enhance(float(f))
+    return im
+
+
+def _pil_blur(im, radius):
+    from PIL import ImageFilter
+    return im.filter(ImageFilter.GaussianBlur(radius=float(radius)))
+
+
+def _u8_images(u8, what):
+    if not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3:
+        raise ValueError("%s: need a uint8 [B, H, W, 3] tensor" % what)
+    if u8.is_cuda:
+        from . import imageprep
+        if u8.shape[1] != u8.shape[2]:
+            raise ValueError("%s: a device batch must be square, got %s" % (what, tuple(u8.shape)))
+        if u8.shape[0]:
+            imageprep.check_size(u8.shape[1])
+        if not u8.is_contiguous():
+            raise ValueError("%s: a device batch must be contiguous (the kernels work in place)" % what)
+
+
+def _pil_each(u8, fn):
+    """u8[i] = fn(i, PIL image of u8[i]) for a CPU batch, in place."""
+    import numpy as np
+    from PIL import Image
+    for i in range(u8.shape[0]):
+        im = fn(i, Image.fromarray(u8[i].contiguous().numpy()))
+        if im is not None:
+            u8[i] = torch.from_numpy(np.array(im, dtype=np.uint8))
+    return u8
+
+
+def color_jitter(u8, ops, factors):
+    """ColorJitter IN PLACE on u8 = uint8 [B, S, S, 3]; returns u8.  ops int [B, 3]: the chain of image i in the order it is applied (0 none,
+    1 brightness, 2 contrast, 3 saturation: imageprep.JITTER_OPS / jitter_table); factors [B, 3]: the enhancement factors, finite and
+    >= 0.  Each step is PIL's ImageEnhance (what torchvision's ColorJitter runs on a PIL image), bit for bit: on a CUDA device
+    op_image_color_jitter (S a multiple of 16 in [16, 1024]), on the CPU PIL itself.  Hue is not provided (the reference passes hue = 0)."""
+    from . import imageprep
+    _u8_images(u8, "color_jitter")
+    tab_ops, tab_f = imageprep.check_jitter((ops, factors), u8.shape[0])
+    if u8.is_cuda:
+        return hip.image_color_jitter(u8, tab_ops, tab_f)
+    return _pil_each(u8, lambda i, im: _pil_jitter(im, tab_ops[i], tab_f[i]) if tab_ops[i].any() else None)
+
+
+def gaussian_blur(u8, radii):
+    """ImageFilter.GaussianBlur(radius) IN PLACE on u8 = uint8 [B, S, S, 3]; returns u8.  radii: one per image, None or <= 0 = not blurred.
+    On a CUDA device op_image_gaussian_blur (S a multiple of 16 in [16, 1024]; radii up to a box radius of 32, i.e. ~33), on the CPU PIL
+    itself; bit for bit the same."""
+    from . import imageprep
+    _u8_images(u8, "gaussian_blur")
+    radii = list(radii.tolist() if hasattr(radii, "tolist") else radii)
+    if len(radii) != u8.shape[0]:
+        raise ValueError("gaussian_blur: need one radius per image, got %d for %d images" % (len(radii), u8.shape[0]))
+    table = imageprep.blur_table(radii)
+    if u8.is_cuda:
+        return hip.image_gaussian_blur(u8, *table)
+    return _pil_each(u8, lambda i, im: _pil_blur(im, radii[i]) if table[3][i] else None)
+
+
+def normalize_images(u8, mean=None, std=None, dtype=torch.float32, flips=None):
+    """[B, 3, S, S] in `dtype` from u8 = uint8 [B, S, S, 3]: ToTensor and Normalize in torchvision's fp32 order ((u / 255 - mean) / std, CLIP
+    mean / std by default), RandomHorizontalFlip where flips[i] is set, then the cast.  On a CUDA device op_image_normalize_flip -- the
+    store of the resize kernel, so both routes share one arithmetic -- on the CPU imageprep.to_tensor_normalize."""
+    from . import imageprep
+    _u8_images(u8, "normalize_images")
+    mean = imageprep.CLIP_MEAN if mean is None else tuple(mean)
+    std = imageprep.CLIP_STD if std is None else tuple(std)
+    if flips is not None and not (u8.is_cuda and torch.is_tensor(flips) and flips.is_cuda):  # (flags already on the device stay there)
+        flips = imageprep.check_flips(flips, u8.shape[0])
+    if u8.is_cuda:
+        kdt = dtype if dtype in (torch.bfloat16, torch.float32) else torch.float32
+        return hip.image_normalize_flip(u8, mean, std, kdt, flips).to(dtype)
+    if flips is not None and any(flips):
+        u8 = torch.where(torch.tensor(flips).view(-1, 1, 1, 1), u8.flip(2), u8)
+    return imageprep.to_tensor_normalize(u8, mean, std).to(dtype)
 
 
 # --------------------------------------------------------------------------------------------------------------
