@@ -613,6 +613,51 @@ int op_image_gaussian_blur(void* img, int64_t B, int64_t S, const int* R, const 
 int op_image_normalize_flip(const void* src, int64_t B, int64_t S, const float* mean, const float* stdev, void* out, int out_dtype,
                             const uint8_t* flip, void* stream);
 
+/* ---- RandAugment and RandomErasing of timm's create_transform (csrc/randaugment.hip) -------------------------------------------------
+ * The two steps of the reference's default image-classification train transform that the entries above do not cover
+ * (data/vision_data/image_classify_dataset.py:65-77: timm.data.create_transform(auto_augment='rand-m9-mstd0.5-inc1',
+ * interpolation='bicubic', re_prob=0.25, re_mode='pixel', re_count=1)).  timm's RandAugment ops are Pillow calls on the resized image;
+ * every op below gives Pillow's bytes.  Additive: op_abi_version() stays 10, no existing entry point changed.
+ *
+ * op_image_randaug_layer, in place on img = dense uint8 [B, S, S, 3]: ONE RandAugment layer, i.e. one op per image.  16 <= S <= 1024,
+ * S % 16 == 0, 0 <= B <= 65535, img and scratch 16-byte aligned.  op int32 [B] and arg fp64 [B, 6] are DEVICE tables, op_host / arg_host
+ * the same tables in HOST memory (validated here, decide the launches); fill: HOST uint8[3], the colour of Affine's uncovered pixels;
+ * hist: DEVICE uint32 [B, 3, 256] workspace, zeroed and filled here; scratch: DEVICE uint8 [B, S, S, 3], not overlapping img.
+ * Per channel c and byte p:
+ *    1 AutoContrast  ImageOps.autocontrast: lo / hi = first / last non-empty bin of the channel's histogram; hi <= lo: unchanged; else in
+ *                    fp64 scale = 255.0 / (hi - lo), offset = -lo * scale, lut[i] = clamp((int)(i * scale + offset), 0, 255) -- a rounded
+ *                    product, a rounded sum, truncation toward zero
+ *    2 Equalize      ImageOps.equalize: fewer than two non-empty bins: unchanged; step = (S S - count of the last non-empty bin) / 255;
+ *                    0: unchanged; else lut[i] = min(255, (step / 2 + the counts of the bins below i) / step), integers only
+ *    3 Invert        255 - p
+ *    4 Posterize     p & ~(2^(8 - bits) - 1), bits = arg[0] in 0 ... 7 (timm returns the image for bits >= 8: that is op 0)
+ *    5 Solarize      p < thresh ? p : 255 - p, thresh = arg[0] in 0 ... 256
+ *    6 SolarizeAdd   p < 128 ? min(255, p + add) : p, add = arg[0] in 0 ... 255
+ *   10 Sharpness     ImageEnhance.Sharpness: d = ImageFilter.SMOOTH of the layer's input = (2 s + 13) / 26 in integers, s = the 3 x 3 sum
+ *                    with centre weight 5, the one-pixel border copied; then Image.blend(d, p, (float)arg[0]), the two-rounding fp32 blend
+ *                    of op_image_color_jitter (one device function serves both)
+ *   11 Affine        Image.transform(size, AFFINE, arg[0 ... 5], BICUBIC, fillcolor=fill): for output pixel (x, y), in fp64 with one rounding
+ *                    per operation, xin = a0 (x + 0.5) + a1 (y + 0.5) + a2, yin = a3 (x + 0.5) + a4 (y + 0.5) + a5; outside [0, S): fill;
+ *                    else the 4 x 4 bicubic of Geometry.c around (xin - 0.5, yin - 0.5) -- columns clamped, row 0 clamped, a later row
+ *                    outside the image repeats the row value before it -- and the byte is 0 for v <= 0, 255 for v >= 255, else (uint8)v
+ *                    (truncated).  Rotate, ShearX / Y and TranslateX / Y are this op with the coefficients of imageprep.affine_coeffs.
+ * Codes 7 Color, 8 Contrast, 9 Brightness are op_image_color_jitter's ops 3, 2, 1 and are refused here.  An image with op 0 is neither read
+ * nor written; a batch of such images launches nothing.  Launches: the histograms (integer atomics: two runs give the same bits; a bin
+ * holds at most 2^20; only when an image has op 1 or 2), the apply pass (pointwise ops in place through a LUT each workgroup builds in
+ * LDS; ops 10 and 11 read img and write scratch), the copy of the images of ops 10 and 11 back into img (only when one occurs).
+ * OP_EINVAL before any launch: S or B out of range, null, misaligned or overlapping buffers, an op outside 0 ... 6, 10, 11, bits, thresh or
+ * add not an integer in its range, a negative or non-finite sharpness factor, a non-finite affine coefficient.  B == 0 launches nothing.
+ *
+ * op_image_erase, in place on x [B, 3, S, S] bf16 (dtype 0) or f32 (1), 1 <= S <= 16384: RandomErasing's store,
+ *   x[i, :, top:top+h, left:left+w] = noise_i.view(3, h, w).to(x.dtype), i.e. element [c, top + r, left + q] = noise[noise_off[i] + (c h + r) w + q],
+ * a bf16 value ONE round-to-nearest-even cast.  box int32 [B, 4] = (top, left, h, w), h = 0: untouched; noise fp32 (3 h w values per erased
+ * image) and noise_off int64 [B] are DEVICE buffers, box_host the boxes in HOST memory.  One launch; none when no image is erased.
+ * OP_EINVAL before the launch: unknown dtype, S or B out of range, null or misaligned pointers, a box with h < 0, w < 1 or outside the image. */
+int op_image_randaug_layer(void* img, int64_t B, int64_t S, const int* op, const double* arg, const int* op_host, const double* arg_host,
+                           const uint8_t* fill, unsigned* hist, void* scratch, void* stream);
+int op_image_erase(void* x, int dtype, int64_t B, int64_t S, const int* box, const int* box_host, const float* noise,
+                   const int64_t* noise_off, void* stream);
+
 /* ---- audio pre-processing: channel mean + whole-clip layer norm + crop / tile / pad (csrc/audioprep.hip) -----------------------
  * Replaces the host loop of one_peace/models/one_peace/hub_interface.py:170-193 and data/base_dataset.py:84-102 (audio_postprocess:
  * feats.mean(-1), F.layer_norm(feats, feats.shape) over the WHOLE clip, crop to max_len samples from the start, repeat the normalised

@@ -25,6 +25,7 @@
 // (4 x 3072 B) and a column strip 4 pixels wide (1024 x 12 B).
 #include "common.h"
 #include "image_store.h"
+#include "photometric_blend.h"
 
 #include <algorithm>
 #include <cmath>
@@ -46,16 +47,6 @@ __device__ __forceinline__ PmChain pm_chain(const int* __restrict__ ops, const f
 }
 
 __device__ __forceinline__ int pm_luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
-
-// Image.blend(d, p, f) for one byte: fadd_rn(d, fmul_rn(f, p - d)).  Written as a plain product and sum under contract(off), as
-// csrc/augment.hip does: __fmul_rn / __fadd_rn are inlined header functions whose * and + the compiler still contracts into an fma (it did:
-// v_fma_f32 in the listing, and about 0.5 % of random bytes off PIL); the pragma binds only what is written here.
-__device__ __forceinline__ int pm_blend(int d, int p, float f) {
-#pragma clang fp contract(off)
-  const float prod = f * (float)(p - d);
-  const float t = (float)d + prod;
-  return (int)fminf(fmaxf(t, 0.0f), 255.0f);
-}
 
 // ops [0, n) of the chain on one pixel; m = the contrast mean (used only when a contrast op is among them)
 __device__ __forceinline__ void pm_apply(const PmChain& c, int n, int m, int (&px)[3]) {

@@ -7,7 +7,7 @@ fallback here: if the library is missing, loading fails loudly.
 """
 import ctypes
 import os
-from ctypes import c_double, c_float, c_int, c_int64, c_void_p
+from ctypes import c_double, c_float, c_int, c_int64, c_ubyte, c_void_p
 
 import torch
 
@@ -109,6 +109,8 @@ SIGNATURES = {
     "op_image_color_jitter": (c_int, [P, I64, I64, P, P, P, P, P, P]),
     "op_image_gaussian_blur": (c_int, [P, I64, I64, P, P, P, P, P, P, P]),
     "op_image_normalize_flip": (c_int, [P, I64, I64, P, P, P, c_int, P, P]),
+    "op_image_randaug_layer": (c_int, [P, I64, I64, P, P, P, P, P, P, P, P]),
+    "op_image_erase": (c_int, [P, c_int, I64, I64, P, P, P, P, P]),
     "op_audio_normalize_pad": (c_int, [P, I64, P, P, I64, I64, I64, P, I64, c_int, P, I64, P]),
     "op_audio_resample": (c_int, [P, I64, P, P, I64, P, I64, P, I64, P]),
     "op_average_precision_workspace_bytes": (I64, [I64, I64]),
@@ -1502,6 +1504,66 @@ def image_normalize_flip(u8, mean, std, dtype=torch.float32, flips=None):
         _check(lib().op_image_normalize_flip(ptr(u8), B, S, (c_float * 3)(*mean), (c_float * 3)(*std), ptr(out), _IMAGE_OUT[dtype], ptr(flips),
                                              stream()), "op_image_normalize_flip")
     return out
+
+
+def image_randaug_layer(u8, ops, args, fill, scratch=None):
+    """op_image_randaug_layer IN PLACE on u8 [B, S, S, 3] (uint8, contiguous, CUDA): one RandAugment layer, ops int32 [B] (imageprep.RANDAUG_OPS;
+    not 7 ... 9, which are op_image_color_jitter's) with args fp64 [B, 6] (host arrays), fill = the three bytes of Affine's uncovered pixels.
+    The tables and the histogram workspace go to the device as ONE buffer; scratch: a uint8 tensor of u8's size to reuse between layers.
+    Returns u8."""
+    import numpy as np
+    B, S = _u8_batch(u8, "image_randaug_layer")
+    ops = np.ascontiguousarray(np.asarray(ops, dtype=np.int32).reshape(B))
+    args = np.ascontiguousarray(np.asarray(args, dtype=np.float64).reshape(B, 6))
+    if B == 0 or not ops.any():
+        return u8
+    fill = (c_ubyte * 3)(*[int(v) for v in fill])
+    uses_hist = bool(((ops == 1) | (ops == 2)).any())
+    head = 8 * B  # int64 words: args [6 B], ops [B / 2, padded to B], then the histograms
+    host = np.zeros(head + (384 * B if uses_hist else 0), dtype=np.int64)
+    host[:6 * B] = args.view(np.int64).reshape(-1)
+    host[6 * B:8 * B].view(np.int32)[:B] = ops
+    with torch.cuda.device(u8.device):
+        dev = torch.from_numpy(host).to(u8.device)
+        base = dev.data_ptr()
+        if scratch is None:
+            scratch = torch.empty_like(u8)
+        _req(scratch, "scratch", torch.uint8)
+        if scratch.numel() != u8.numel():
+            raise ValueError("image_randaug_layer: the scratch must have u8's size")
+        # (without a histogram op the workspace is never read or written: it stands on the tables)
+        _check(lib().op_image_randaug_layer(ptr(u8), B, S, c_void_p(base + 48 * B), c_void_p(base), ops.ctypes.data_as(c_void_p),
+                                            args.ctypes.data_as(c_void_p), fill, c_void_p(base + (64 * B if uses_hist else 0)), ptr(scratch),
+                                            stream()), "op_image_randaug_layer")
+    return u8
+
+
+def image_erase(x, boxes, noise, noise_off):
+    """op_image_erase IN PLACE on x [B, 3, S, S] bf16 / fp32 (contiguous, CUDA): x[i, :, top:top+h, left:left+w] = the 3 h w fp32 values of
+    `noise` (a CUDA fp32 tensor) at noise_off[i], cast once; boxes int32 [B, 4] (top, left, h, w; h = 0: untouched) and noise_off int64 [B]
+    are host arrays, staged in ONE buffer.  Returns x."""
+    import numpy as np
+    _req(x, "x")
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+        raise ValueError("image_erase: need x [B, 3, S, S], got %s" % (tuple(x.shape),))
+    B, S = x.shape[0], x.shape[2]
+    boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(B, 4))
+    offs = np.ascontiguousarray(np.asarray(noise_off, dtype=np.int64).reshape(B))
+    if B == 0 or S == 0:
+        return x
+    need = max([0] + [int(o) + 3 * int(b[2]) * int(b[3]) for o, b in zip(offs, boxes) if b[2] > 0])
+    if need and (noise is None or noise.numel() < need or int(offs.min()) < 0):
+        raise ValueError("image_erase: the noise buffer holds %d values, the boxes need %d" % (0 if noise is None else noise.numel(), need))
+    if noise is not None:
+        _req(noise, "noise", torch.float32)
+    host = np.zeros(3 * B, dtype=np.int64)
+    host[:B], host[B:].view(np.int32)[:4 * B] = offs, boxes.reshape(-1)
+    with torch.cuda.device(x.device):
+        dev = torch.from_numpy(host).to(x.device)
+        base = dev.data_ptr()
+        _check(lib().op_image_erase(ptr(x), _dt(x), B, S, c_void_p(base + 8 * B), boxes.ctypes.data_as(c_void_p), ptr(noise), c_void_p(base),
+                                    stream()), "op_image_erase")
+    return x
 
 
 def audio_normalize_pad(packed, dtype=torch.float32, device=None):

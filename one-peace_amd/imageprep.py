@@ -372,6 +372,133 @@ def blur_table(radii):
     return R, ww, fw, on
 
 
+# ---- RandAugment: the host-side tables of op_image_randaug_layer (csrc/randaugment.hip) ----
+# Op codes of a layer's table (include/onepeace_hip.h).  7 ... 9 are ImageEnhance blends: ops.rand_augment hands them to op_image_color_jitter.
+RANDAUG_OPS = {"none": 0, "AutoContrast": 1, "Equalize": 2, "Invert": 3, "Posterize": 4, "Solarize": 5, "SolarizeAdd": 6, "Color": 7,
+               "Contrast": 8, "Brightness": 9, "Sharpness": 10, "Affine": 11}
+RANDAUG_TO_JITTER = {7: JITTER_OPS["saturation"], 8: JITTER_OPS["contrast"], 9: JITTER_OPS["brightness"]}
+AFFINE_NAMES = ("Rotate", "ShearX", "ShearY", "TranslateX", "TranslateY")
+
+
+def affine_coeffs(name, value, size):
+    """The six coefficients of PIL's Image.transform(AFFINE) for timm's geometric RandAugment ops on a size x size image, or None for the
+    identity: ShearX (1, v, 0, 0, 1, 0), ShearY (1, 0, 0, v, 1, 0), TranslateX (1, 0, v, 0, 1, 0) and TranslateY (1, 0, 0, 0, 1, v) with v
+    in pixels, and Rotate by `value` degrees with Image.rotate's matrix about (size / 2, size / 2): the angle taken modulo 360, cosine and
+    sine rounded to 15 decimals, the translation evaluated as PIL evaluates it.  angle % 360 == 0 is the identity (PIL copies the image);
+    the other multiples of 90 are a ValueError: there PIL transposes instead of resampling.  ValueError: an unknown name, a value that is
+    not finite."""
+    v = float(value)
+    if name not in AFFINE_NAMES:
+        raise ValueError("affine_coeffs: unknown op %r (need one of %s)" % (name, ", ".join(AFFINE_NAMES)))
+    if not math.isfinite(v):
+        raise ValueError("affine_coeffs: %s: the value must be finite, got %r" % (name, value))
+    if name == "ShearX":
+        return (1.0, v, 0.0, 0.0, 1.0, 0.0)
+    if name == "ShearY":
+        return (1.0, 0.0, 0.0, v, 1.0, 0.0)
+    if name == "TranslateX":
+        return (1.0, 0.0, v, 0.0, 1.0, 0.0)
+    if name == "TranslateY":
+        return (1.0, 0.0, 0.0, 0.0, 1.0, v)
+    angle = v % 360.0
+    if angle == 0:
+        return None
+    if angle in (90, 180, 270):
+        raise ValueError("affine_coeffs: Rotate by %r degrees is a transpose in PIL, not a resampling (not provided)" % (value,))
+    cx = cy = size / 2
+    angle = -math.radians(angle)
+    m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0, round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+    x, y = -cx, -cy
+    m[2], m[5] = m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+    m[2] += cx
+    m[5] += cy
+    return tuple(m)
+
+
+def _randaug_row(i, name, vals, size):
+    """(code, the six fp64 arguments) of one op of image i."""
+    zero = (0.0,) * 6
+    if name in AFFINE_NAMES:
+        if len(vals) != 1:
+            raise ValueError("randaug_table: image %d: %s takes one value" % (i, name))
+        if size is None:
+            raise ValueError("randaug_table: image %d: %s needs the image size" % (i, name))
+        co = affine_coeffs(name, vals[0], size)
+        return (0, zero) if co is None else (RANDAUG_OPS["Affine"], co)
+    code = RANDAUG_OPS.get(name) if isinstance(name, str) else (int(name) if int(name) in RANDAUG_OPS.values() else None)
+    if code is None:
+        raise ValueError("randaug_table: image %d: unknown op %r (need one of %s, %s or a code 0 ... 11)" % (
+            i, name, ", ".join(sorted(RANDAUG_OPS)), ", ".join(AFFINE_NAMES)))
+    want = 6 if code == 11 else (0 if code <= 3 else 1)
+    if len(vals) != want and not (want == 0 and len(vals) == 6):
+        raise ValueError("randaug_table: image %d: op %r takes %d value(s), got %d" % (i, name, want, len(vals)))
+    vals = tuple(float(v) for v in vals)
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError("randaug_table: image %d: op %r has an argument that is not finite" % (i, name))
+    if code in (4, 5, 6):
+        lo, hi = {4: (0, None), 5: (0, 256), 6: (0, 255)}[code]
+        v = vals[0]
+        if v != math.floor(v) or v < lo or (hi is not None and v > hi):
+            raise ValueError("randaug_table: image %d: op %r: %r is not an integer in its range" % (i, name, v))
+        if code == 4 and v >= 8:  # timm's posterize returns the image for bits >= 8
+            return 0, zero
+    if code in (7, 8, 9, 10) and (vals[0] < 0.0 or vals[0] > float(np.finfo(np.float32).max)):
+        raise ValueError("randaug_table: image %d: op %r: the factor %r must be >= 0 (and finite as fp32)" % (i, name, vals[0]))
+    if code <= 3:
+        return code, zero
+    return code, (vals + zero)[:6]
+
+
+def randaug_table(layers_per_image, size=None):
+    """(ops int32 [B, L], args fp64 [B, L, 6]) from one list of ops per image, in the order they are applied, e.g.
+    [("ShearX", 0.21), ("Equalize",)]: a name of RANDAUG_OPS with its argument (Posterize bits, Solarize thresh, SolarizeAdd add, the factor
+    of Color / Contrast / Brightness / Sharpness, the six coefficients of Affine), or Rotate (degrees), ShearX / ShearY, TranslateX / TranslateY
+    (pixels), which become Affine through affine_coeffs (they need `size`).  L = the longest list (at least 1); missing layers are op 0.
+    Posterize with bits >= 8 and Rotate by a multiple of 360 are op 0.  ValueError: an unknown name, a wrong number of arguments, an argument
+    that is not finite, bits / thresh / add not an integer in 0 ... / 0 ... 256 / 0 ... 255, a negative factor, Rotate by 90, 180 or 270."""
+    layers = [[] if la is None else list(la) for la in layers_per_image]
+    L = max([1] + [len(la) for la in layers])
+    ops = np.zeros((len(layers), L), dtype=np.int32)
+    args = np.zeros((len(layers), L, 6), dtype=np.float64)
+    for i, la in enumerate(layers):
+        for k, item in enumerate(la):
+            item = tuple(item) if isinstance(item, (tuple, list)) else (item,)
+            if not item:
+                raise ValueError("randaug_table: image %d: an empty op" % i)
+            vals = item[1:]
+            if len(vals) == 1 and isinstance(vals[0], (tuple, list, np.ndarray)):
+                vals = tuple(vals[0])
+            ops[i, k], args[i, k] = _randaug_row(i, item[0], vals, size)
+    return ops, args
+
+
+def check_randaug(randaug, count):
+    """The (ops, args, fill) of `count` images as (int32 [count, L], fp64 [count, L, 6], three ints 0 ... 255), validated as randaug_table
+    validates op codes and arguments."""
+    if len(randaug) != 3:
+        raise ValueError("randaug: need (ops, args, fill)")
+    ops, args, fill = randaug
+    ops = np.asarray(ops.cpu() if torch.is_tensor(ops) else ops)
+    args = np.asarray(args.cpu() if torch.is_tensor(args) else args, dtype=np.float64)
+    if ops.ndim == 1:
+        ops = ops.reshape(-1, 1)
+    if ops.ndim != 2 or ops.shape[0] != count or args.size != ops.size * 6:
+        raise ValueError("randaug: need ops [%d, L] and args [%d, L, 6], got %s and %s" % (count, count, ops.shape, args.shape))
+    args = args.reshape(ops.shape + (6,))
+    fill = tuple(fill)
+    if len(fill) != 3 or any(int(v) != v or not 0 <= v <= 255 for v in fill):
+        raise ValueError("randaug: fill must be three integers in 0 ... 255, got %r" % (fill,))
+    fill = tuple(int(v) for v in fill)
+    if ops.size == 0:
+        return np.zeros(ops.shape, np.int32), np.zeros(ops.shape + (6,), np.float64), fill
+    if (ops != ops.astype(np.int64)).any():
+        raise ValueError("randaug: op codes must be integers")
+    rows = [[(int(o),) + ((tuple(a.tolist()),) if int(o) == 11 else (() if 0 <= int(o) <= 3 else (float(a[0]),))) for o, a in zip(orow, arow)]
+            for orow, arow in zip(ops, args)]
+    tab_ops, tab_args = randaug_table(rows)
+    return tab_ops, tab_args, fill
+
+
 def random_resized_crop_params(height, width, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), generator=None):
     """(top, left, h, w) of torchvision's RandomResizedCrop.get_params for a height x width image, restated with torch's RNG
     (`generator`): up to 10 tries of area * U(scale), exp(U(log ratio)), w = int(round(sqrt(a r))), h = int(round(sqrt(a / r))), the

@@ -682,7 +682,7 @@ def _is_pil(im):
 
 
 def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, device="cpu", crops=None, center_crop=False, flips=None,
-                      jitter=None, blur=None):
+                      jitter=None, blur=None, randaug=None):
     """[B, 3, size, size] in `dtype` on `device` from decoded RGB images (uint8 [H, W, 3] arrays / tensors or PIL images of any
     size): PIL's Image.resize((size, size), BICUBIC), ToTensor and Normalize (CLIP mean / std by default) in torchvision's fp32
     order, then the cast -- the reference's transform, bit for bit.  On a CUDA device this is op_image_resize_normalize
@@ -701,7 +701,13 @@ def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, de
     or <= 0 for an image that is not blurred (augment.GaussianBlur.params).  With either, the device route is the resize to uint8
     [B, size, size, 3], op_image_color_jitter, op_image_gaussian_blur and op_image_normalize_flip with the flips; the CPU route is the same
     chain in PIL, in the reference's Compose order (resize, distortion, blur, flip).  With both None the path and the results are those
-    of the plain resize."""
+    of the plain resize.
+
+    randaug: the (ops, args, fill) tables of rand_augment (augment.RandAugment.params draws them), timm's create_transform order
+    (image_classify_dataset.py:65-77): the flip comes BEFORE RandAugment.  The device route is the resize to uint8 with the flips inside
+    the resize pass, rand_augment, then op_image_normalize_flip without flips; the CPU route the same order in PIL.  Together with
+    jitter or blur it is a ValueError (timm drops the colour jitter when auto_augment is set, and the two positions of the flip must not
+    be mixed).  With randaug=None the paths and the results are those described above."""
     import numpy as np
 
     from . import imageprep
@@ -717,6 +723,10 @@ def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, de
     if flips is not None:
         flips = imageprep.check_flips(flips, len(images))
     photometric = jitter is not None or blur is not None
+    if randaug is not None:
+        if photometric:
+            raise ValueError("preprocess_images: randaug excludes jitter and blur (timm's create_transform drops the colour jitter with auto_augment)")
+        randaug = imageprep.check_randaug(randaug, len(images))
     if jitter is not None:
         jitter = imageprep.check_jitter(jitter, len(images))
     if blur is not None:
@@ -728,6 +738,10 @@ def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, de
     if dev.type == "cuda":
         arrs = [np.asarray(im.convert("RGB")) if _is_pil(im) else im for im in images]
         kdt = dtype if dtype in (torch.bfloat16, torch.float32) else torch.float32
+        if randaug is not None:
+            packed = imageprep.pack_images(arrs, size, crops=crops, center_crop=center_crop, flips=flips)
+            u8 = hip.image_resize_normalize(packed, dtype=torch.uint8, device=dev)
+            return hip.image_normalize_flip(_rand_augment_device(u8, *randaug), mean, std, kdt, None).to(dtype)
         if photometric:
             packed = imageprep.pack_images(arrs, size, crops=crops, center_crop=center_crop)
             u8 = hip.image_resize_normalize(packed, dtype=torch.uint8, device=dev)
@@ -756,6 +770,9 @@ def preprocess_images(images, size, mean=None, std=None, dtype=torch.float32, de
             im = _pil_blur(im, blur_radii[i])
         if flips is not None and flips[i]:
             im = im.transpose(Image.FLIP_LEFT_RIGHT)
+        if randaug is not None:
+            for op, arg in zip(randaug[0][i], randaug[1][i]):
+                im = _pil_randaug(im, op, arg, randaug[2])
         u8 = torch.from_numpy(np.array(im, dtype=np.uint8))
         out.append(imageprep.to_tensor_normalize(u8, mean, std))
     return torch.stack(out).to(device=dev, dtype=dtype) if out else torch.empty(0, 3, size, size, dtype=dtype, device=dev)
@@ -848,6 +865,121 @@ def normalize_images(u8, mean=None, std=None, dtype=torch.float32, flips=None):
     if flips is not None and any(flips):
         u8 = torch.where(torch.tensor(flips).view(-1, 1, 1, 1), u8.flip(2), u8)
     return imageprep.to_tensor_normalize(u8, mean, std).to(dtype)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# RandAugment and RandomErasing of timm's create_transform (data/vision_data/image_classify_dataset.py:65-77; augment.RandAugment /
+# augment.RandomErasing draw the tables)
+# --------------------------------------------------------------------------------------------------------------
+def _pil_randaug(im, op, arg, fill):
+    """One RandAugment op of timm's auto_augment.py on a PIL RGB image, by its code (imageprep.RANDAUG_OPS): the Pillow calls timm makes."""
+    from PIL import Image, ImageEnhance, ImageOps
+    op = int(op)
+    if op == 0:
+        return im
+    if op == 1:
+        return ImageOps.autocontrast(im)
+    if op == 2:
+        return ImageOps.equalize(im)
+    if op == 3:
+        return ImageOps.invert(im)
+    if op == 4:
+        return ImageOps.posterize(im, int(arg[0]))
+    if op == 5:
+        return ImageOps.solarize(im, int(arg[0]))
+    if op == 6:
+        lut = [min(255, i + int(arg[0])) if i < 128 else i for i in range(256)]
+        return im.point(lut + lut + lut)
+    if op in (7, 8, 9, 10):
+        enhancer = {7: ImageEnhance.Color, 8: ImageEnhance.Contrast, 9: ImageEnhance.Brightness, 10: ImageEnhance.Sharpness}[op]
+        return enhancer(im).enhance(float(arg[0]))
+    if op == 11:
+        return im.transform(im.size, Image.AFFINE, tuple(float(v) for v in arg), resample=Image.BICUBIC, fillcolor=tuple(fill))
+    raise ValueError("rand_augment: unknown op code %d" % op)
+
+
+def _rand_augment_device(u8, tab_ops, tab_args, fill):
+    """The layers of validated tables on a device batch: per layer op_image_randaug_layer for its own ops and op_image_color_jitter, with
+    a one-op chain, for the images whose op is Color / Contrast / Brightness.  An image has one op per layer, so the two calls of a
+    layer touch different images."""
+    import numpy as np
+
+    from . import imageprep
+    B = u8.shape[0]
+    if B == 0 or not tab_ops.any():
+        return u8
+    scratch = torch.empty_like(u8) if (tab_ops == 10).any() or (tab_ops == 11).any() else u8.new_empty(0)
+    for layer in range(tab_ops.shape[1]):
+        ops_l, args_l = tab_ops[:, layer], tab_args[:, layer]
+        enhance = (ops_l >= 7) & (ops_l <= 9)
+        own = np.where(enhance, 0, ops_l).astype(np.int32)
+        if own.any():
+            if scratch.numel() == 0:  # (the entry wants a scratch even when no op of the layer writes it)
+                scratch = torch.empty_like(u8)
+            hip.image_randaug_layer(u8, own, args_l, fill, scratch)
+        if enhance.any():
+            chain = np.zeros((B, 3), dtype=np.int32)
+            factors = np.ones((B, 3), dtype=np.float32)
+            chain[enhance, 0] = [imageprep.RANDAUG_TO_JITTER[int(o)] for o in ops_l[enhance]]
+            factors[enhance, 0] = args_l[enhance, 0]
+            hip.image_color_jitter(u8, chain, factors)
+    return u8
+
+
+def rand_augment(u8, ops, args, fill):
+    """RandAugment IN PLACE on u8 = uint8 [B, S, S, 3]; returns u8.  ops int [B, L] and args fp64 [B, L, 6]: the L layers of image i in the
+    order they are applied (imageprep.RANDAUG_OPS / randaug_table; augment.RandAugment.params draws them), fill: the three bytes Affine
+    gives the pixels it does not cover.  Every op is the Pillow call timm's auto_augment.py makes (ImageOps, ImageEnhance,
+    Image.transform(AFFINE, BICUBIC) with Image.rotate's matrix), byte for byte: on a CUDA device op_image_randaug_layer and, for Color /
+    Contrast / Brightness, op_image_color_jitter, layer by layer (S a multiple of 16 in [16, 1024]); on the CPU Pillow itself."""
+    from . import imageprep
+    _u8_images(u8, "rand_augment")
+    tab_ops, tab_args, fill = imageprep.check_randaug((ops, args, fill), u8.shape[0])
+    if u8.is_cuda:
+        return _rand_augment_device(u8, tab_ops, tab_args, fill)
+
+    def each(i, im):
+        if not tab_ops[i].any():
+            return None
+        for op, arg in zip(tab_ops[i], tab_args[i]):
+            im = _pil_randaug(im, op, arg, fill)
+        return im
+    return _pil_each(u8, each)
+
+
+def erase_images(x, boxes, noise):
+    """RandomErasing's store IN PLACE on x [B, 3, H, W]; returns x.  boxes int [B, 4] = (top, left, h, w) per image, h = 0 for an image
+    that is not erased; noise: ONE fp32 tensor on x's device holding the 3 h w values of every erased image back to back, in the order of
+    the batch.  x[i, :, top:top+h, left:left+w] = noise_i.view(3, h, w).to(x.dtype) (timm/data/random_erasing.py), bit for bit: on a CUDA
+    device op_image_erase in one launch (square bf16 / fp32 batches; anything else is a ValueError), on the CPU the torch statement.
+    ValueError: a box outside the image, a noise buffer of the wrong size."""
+    import numpy as np
+    if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError("erase_images: x must be [B, 3, H, W]")
+    B, _, H, W = x.shape
+    boxes = np.asarray(boxes.cpu() if torch.is_tensor(boxes) else boxes, dtype=np.int64).reshape(-1, 4)
+    if boxes.shape[0] != B:
+        raise ValueError("erase_images: need one (top, left, h, w) per image, got %d for %d images" % (boxes.shape[0], B))
+    offs, total = np.zeros(B, dtype=np.int64), 0
+    for i, (top, left, h, w) in enumerate(boxes.tolist()):
+        offs[i] = total
+        if h == 0:
+            continue
+        if h < 0 or w < 1 or top < 0 or left < 0 or top + h > H or left + w > W:
+            raise ValueError("erase_images: box %d (top %d, left %d, h %d, w %d) is empty or outside the %d x %d image" % (i, top, left, h, w, H, W))
+        total += 3 * h * w
+    have = 0 if noise is None else noise.numel()
+    if have != total or (total and (noise.dtype != torch.float32 or noise.device != x.device)):
+        raise ValueError("erase_images: noise must be fp32 on x's device with %d values (3 h w per erased image), got %d" % (total, have))
+    if x.is_cuda:
+        if H != W or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_contiguous():
+            raise ValueError("erase_images: a device batch must be square, contiguous and fp32 or bf16, got %s %s" % (x.dtype, tuple(x.shape)))
+        return hip.image_erase(x, boxes, noise.contiguous().view(-1) if total else None, offs)
+    flat = noise.reshape(-1) if total else None
+    for i, (top, left, h, w) in enumerate(boxes.tolist()):
+        if h > 0:
+            x[i, :, top:top + h, left:left + w] = flat[offs[i]:offs[i] + 3 * h * w].view(3, h, w).to(x.dtype)
+    return x
 
 
 # --------------------------------------------------------------------------------------------------------------
