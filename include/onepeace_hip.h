@@ -786,6 +786,43 @@ int op_attn_pool_bwd(const void* dout, const void* k, const void* v, int64_t ld,
                      void* dk, void* dv, int64_t ldg, int64_t batch_stride_g, float* dq_part, int64_t B, int64_t S, int64_t heads,
                      int64_t hd, void* stream);
 
+/* ---- pretraining masks: whole words, image patches, audio blocks (csrc/masks.hip) --------------------------------------------------
+ * Additive: op_abi_version() stays 10, no existing entry point changed.
+ * Every random choice is select(candidates, k, keys): the k items first in the order (key descending, index ascending) over the
+ * candidates; the row's other items follow them in index order.  Keys are int32 >= 0 (the sign bit is ignored).  The outputs are a pure
+ * function of (inputs, keys, counts): no atomics, no global scratch, two runs give the same bits.  One workgroup per (row, mask kind)
+ * sorts the row's keys in LDS (bitonic, next power of two) and compacts the kept positions by ballot and popcount.
+ * Layout of every mask: uint8 (torch.bool) [B, S], S = items + 1; position 0 is CLS and never masked, item t sits at position t + 1,
+ * positions beyond the row's own length are False.  ids: int64 [B, width], the ascending positions of the row with mask False (padding
+ * positions left out), then -1: what collate_fn (one_peace/data/__init__.py:50-81, merge(..., pad=-1)) gives.
+ * Limits: at most 4096 items per row, B < 2^31; OP_EINVAL with a message before anything is launched otherwise.  B == 0 returns without
+ * a launch.
+ * op_mask_patches replaces one_peace/data/pretrain_data/image_text_pretrain_dataset.py:85-94 and :99-104.  keys_a, keys_b: [B, N].
+ * mask = select(all, m1, keys_a), ids [B, N + 1 - m1].  vl_mask = (not masked) U select(masked, extra, keys_b), vl_ids [B, m1 - extra + 1];
+ * 0 <= extra <= m1 <= N.  keys_b, vl_mask and vl_ids may all be NULL: the first mask alone.
+ * op_mask_words replaces add_whole_word_mask (image_text_pretrain_dataset.py:121-139, audio_text_pretrain_dataset.py:98-116) and
+ * image_text_pretrain_dataset.py:73-77, :97-98, :101-102.  src_tokens: int64 [B, L], row stride ld: the caption's tokens, eos, then
+ * `pad`.  n = (tokens != pad) - 1 (0 for an all-pad row); positions 0 ... n + 1 belong to the row.  table: uint8 [vocab];
+ * ws[t] = table[token t] != 0 for t < n (a token outside [0, vocab) starts no word), W = sum ws, k = ceil(float32(W) * p) in fp32 as
+ * torch rounds is_word_start.float().sum() * p.  The k starts select(ws, k, keys_a) are masked, each with the tokens after it up to the
+ * next start or the caption's end.  A row with n == 0 or W == 0 gets no masked token (the reference asserts).  With keys_b, vl_mask,
+ * vl_ids: vl_mask = select(tokens not masked, int(n * vl_ratio), keys_b), the product in fp64; masked tokens follow in index order when
+ * fewer are unmasked.  counts: int32 [2, B] (kind, row) = the row's kept positions; a row that keeps more than width (vl_width) positions
+ * has its ids truncated to the first width, never written out of bounds.  keys_a, keys_b: [B, L].  0 <= p, vl_ratio <= 1.
+ * op_mask_blocks replaces one_peace/utils/data_utils.py:147-175 and :187-226 (compute_block_mask_1d: overlapping blocks,
+ * require_same_masks, no expand_adjcent, mask_dropout or inverse_mask) and audio_text_pretrain_dataset.py:77-78, :81-82.
+ * rows: int32 [B, 3] = (T, K, target) per clip, on the device, and rows_host, the same table in host memory, which is what is checked:
+ * 0 <= T <= Tmax, 0 <= K <= Kmax, 0 <= target <= T, T + 1 - target <= width.  centers: int32 [B, Kmax]; keys: [B, Tmax].
+ * Frames clamp(c + i - length / 2, 0, T - 1), i < length, are masked for each of the row's first K centres; with n masked frames,
+ * n > target unmasks select(masked, n - target, keys), n < target masks select(unmasked, target - n, keys). */
+int op_mask_patches(const int* keys_a, const int* keys_b, int64_t B, int64_t N, int64_t m1, int64_t extra, uint8_t* mask, int64_t* ids,
+                    uint8_t* vl_mask, int64_t* vl_ids, void* stream);
+int op_mask_words(const int64_t* src_tokens, int64_t ld, int64_t B, int64_t L, int64_t pad, const uint8_t* table, int64_t vocab,
+                  const int* keys_a, const int* keys_b, float p, double vl_ratio, uint8_t* mask, int64_t* ids, int64_t width,
+                  uint8_t* vl_mask, int64_t* vl_ids, int64_t vl_width, int* counts, void* stream);
+int op_mask_blocks(const int* rows, const int* rows_host, const int* centers, int64_t Kmax, const int* keys, int64_t Tmax, int64_t B,
+                   int64_t length, uint8_t* mask, int64_t* ids, int64_t width, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

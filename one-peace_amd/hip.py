@@ -119,6 +119,9 @@ SIGNATURES = {
     "op_box_loss": (c_int, [P, c_int, P, I64, c_float, P, P, P]),
     "op_attn_pool_fwd": (c_int, [P, P, I64, I64, P, P, I64, P, P, I64, I64, I64, I64, P]),
     "op_attn_pool_bwd": (c_int, [P, P, P, I64, I64, P, P, P, P, I64, I64, P, I64, I64, I64, I64, P]),
+    "op_mask_patches": (c_int, [P, P, I64, I64, I64, I64, P, P, P, P, P]),
+    "op_mask_words": (c_int, [P, I64, I64, I64, I64, P, I64, P, P, c_float, c_double, P, P, I64, P, P, I64, P, P]),
+    "op_mask_blocks": (c_int, [P, P, P, I64, P, I64, I64, I64, P, P, I64, P]),
 }
 
 
@@ -1767,6 +1770,102 @@ def attn_pool_bwd(dout, k, v, q, p, dk=None, dv=None, dq_part=None):
     _check(lib().op_attn_pool_bwd(ptr(dout), ptr(k), ptr(v), ld, bs, ptr(q), ptr(p), ptr(dk), ptr(dv), ldg, bsg, ptr(dq_part), B, S, heads,
                                   hd, stream()), "op_attn_pool_bwd")
     return dk, dv, dq_part
+
+
+MASK_MAX_ITEMS = 4096  # csrc/masks.hip: MK_MAX, the items (positions without CLS) of one row
+
+
+def _check_mask(rc, what):
+    if rc == -22:  # OP_EINVAL: a bad argument of the caller
+        msg = lib().op_last_error()
+        raise ValueError(msg.decode() if msg else what)
+    _check(rc, what)
+
+
+def _mask_out(out, i, shape, dtype, device, name):
+    t = None if out is None else out[i]
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _req(t, name, dtype)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: need shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    return t
+
+
+def mask_patches(keys_a, m1, keys_b=None, extra=0, out=None):
+    """op_mask_patches.  keys_a (and keys_b, for the vl mask) int32 [B, N] (contiguous, CUDA).  Returns (mask bool [B, N + 1],
+    ids int64 [B, N + 1 - m1], vl_mask bool [B, N + 1] or None, vl_ids int64 [B, m1 - extra + 1] or None).  out: a 4-tuple of tensors to
+    write into (entries may be None)."""
+    _req(keys_a, "keys_a", torch.int32)
+    _req(keys_b, "keys_b", torch.int32)
+    if keys_a.dim() != 2 or (keys_b is not None and keys_b.shape != keys_a.shape):
+        raise ValueError("mask_patches: need keys_a [B, N] and keys_b of the same shape")
+    B, N = keys_a.shape
+    m1, extra = int(m1), int(extra)
+    if not 0 <= m1 <= N or (keys_b is not None and not 0 <= extra <= m1):
+        raise ValueError("mask_patches: need 0 <= extra <= m1 <= N, got extra %d, m1 %d, N %d" % (extra, m1, N))
+    dev, vl = keys_a.device, keys_b is not None
+    with torch.cuda.device(dev):
+        mask = _mask_out(out, 0, (B, N + 1), torch.bool, dev, "mask")
+        ids = _mask_out(out, 1, (B, N + 1 - m1), torch.int64, dev, "ids")
+        vl_mask = _mask_out(out, 2, (B, N + 1), torch.bool, dev, "vl_mask") if vl else None
+        vl_ids = _mask_out(out, 3, (B, m1 - extra + 1), torch.int64, dev, "vl_ids") if vl else None
+        _check_mask(lib().op_mask_patches(ptr(keys_a), ptr(keys_b), B, N, m1, extra, ptr(mask), ptr(ids), ptr(vl_mask), ptr(vl_ids), stream()),
+                    "op_mask_patches")
+    return mask, ids, vl_mask, vl_ids
+
+
+def mask_words(src_tokens, table, keys_a, p, keys_b=None, vl_ratio=0.0, pad=1, width=None, vl_width=None, out=None):
+    """op_mask_words.  src_tokens int64 [B, L] (rows may be strided), table uint8 [vocab], keys_a / keys_b int32 [B, L] (CUDA).
+    width / vl_width: the columns of the ids, None = L + 1 (every row fits).  Returns (mask bool [B, L + 1], ids int64 [B, width],
+    vl_mask, vl_ids (None without keys_b), counts int32 [2, B]: the kept positions of each row, which may exceed the width given: the ids
+    of such a row are truncated).  Nothing is synchronised.  out: a 5-tuple of tensors to write into (entries may be None)."""
+    _req(table, "table", torch.uint8)
+    _req(keys_a, "keys_a", torch.int32)
+    _req(keys_b, "keys_b", torch.int32)
+    if not src_tokens.is_cuda or src_tokens.dtype != torch.int64 or src_tokens.dim() != 2 or (src_tokens.shape[1] > 1 and src_tokens.stride(1) != 1):
+        raise ValueError("mask_words: src_tokens must be a CUDA int64 [B, L] tensor with unit column stride")
+    B, L = src_tokens.shape
+    if tuple(keys_a.shape) != (B, L) or (keys_b is not None and tuple(keys_b.shape) != (B, L)):
+        raise ValueError("mask_words: keys must have the shape of src_tokens, %s" % ((B, L),))
+    ld = src_tokens.stride(0) if B > 1 else L
+    dev, vl = src_tokens.device, keys_b is not None
+    width = L + 1 if width is None else int(width)
+    vl_width = L + 1 if vl_width is None else int(vl_width)
+    with torch.cuda.device(dev):
+        mask = _mask_out(out, 0, (B, L + 1), torch.bool, dev, "mask")
+        ids = _mask_out(out, 1, (B, width), torch.int64, dev, "ids")
+        vl_mask = _mask_out(out, 2, (B, L + 1), torch.bool, dev, "vl_mask") if vl else None
+        vl_ids = _mask_out(out, 3, (B, vl_width), torch.int64, dev, "vl_ids") if vl else None
+        counts = _mask_out(out, 4, (2, B), torch.int32, dev, "counts")
+        _check_mask(lib().op_mask_words(ptr(src_tokens), ld, B, L, int(pad), ptr(table), table.numel(), ptr(keys_a), ptr(keys_b), float(p),
+                                        float(vl_ratio), ptr(mask), ptr(ids), width, ptr(vl_mask), ptr(vl_ids), vl_width if vl else 0,
+                                        ptr(counts), stream()), "op_mask_words")
+    return mask, ids, vl_mask, vl_ids, counts
+
+
+def mask_blocks(rows, centers, keys, length, width=None, out=None):
+    """op_mask_blocks.  rows: a host int32 [B, 3] array of (T, K, target) per clip; centers int32 [B, Kmax], keys int32 [B, Tmax] (CUDA).
+    width: the columns of the ids, None = max(T + 1 - target).  Returns (mask bool [B, Tmax + 1], ids int64 [B, width]).  The table goes
+    to the device in one copy.  out: a 2-tuple of tensors to write into."""
+    import numpy as np
+    _req(centers, "centers", torch.int32)
+    _req(keys, "keys", torch.int32)
+    if keys.dim() != 2 or centers.dim() != 2 or centers.shape[0] != keys.shape[0]:
+        raise ValueError("mask_blocks: need centers [B, Kmax] and keys [B, Tmax]")
+    B, Tmax = keys.shape
+    Kmax = centers.shape[1]
+    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(B, 3))
+    if width is None:
+        width = int((rows[:, 0] + 1 - rows[:, 2]).max()) if B else 1
+    dev = keys.device
+    with torch.cuda.device(dev):
+        mask = _mask_out(out, 0, (B, Tmax + 1), torch.bool, dev, "mask")
+        ids = _mask_out(out, 1, (B, int(width)), torch.int64, dev, "ids")
+        rows_dev = torch.from_numpy(rows).to(dev)
+        _check_mask(lib().op_mask_blocks(ptr(rows_dev), rows.ctypes.data_as(c_void_p), ptr(centers) if Kmax else None, Kmax, ptr(keys), Tmax, B,
+                                         int(length), ptr(mask), ptr(ids), int(width), stream()), "op_mask_blocks")
+    return mask, ids
 
 
 def mfma_rate_probe(seconds=1.0, waves_per_cu=8, data="normal", device=None):

@@ -2506,3 +2506,197 @@ def attention_pool(k, v, q, key_padding_mask=None):
                     pad = pad.contiguous()
             return AttentionPoolFn.apply(k, v, q.reshape(heads, hd).contiguous(), pad)
     return attention_pool_torch(k, v, q, key_padding_mask)
+
+
+# --------------------------------------------------------------------------------------------------------------
+# pretraining masks (csrc/masks.hip; pretrain_masks.py draws the keys): every random choice is select(candidates, k, keys)
+# --------------------------------------------------------------------------------------------------------------
+def _select_rank(cand, keys, in_row=None):
+    """The place of every item of a row in the order of select(): candidates by (key descending, index ascending), then the row's other
+    items by index, then what lies beyond the row.  cand, in_row: bool [B, n]; keys: int [B, n], non-negative.  int64 [B, n]."""
+    B, n = keys.shape
+    idx = torch.arange(n, device=keys.device)
+    word = (torch.where(cand, (keys.long() & 0x7FFFFFFF) + 1, torch.zeros((), dtype=torch.int64, device=keys.device)) << 31) | (0x7FFFFFFF - idx)
+    if in_row is not None:
+        word = torch.where(in_row, word, torch.full((), -1, dtype=torch.int64, device=keys.device))
+    order = torch.argsort(word, dim=1, descending=True, stable=True)
+    rank = torch.empty_like(order)
+    rank.scatter_(1, order, idx.expand(B, n).contiguous())
+    return rank
+
+
+def _preserve_ids(mask, rowlen, width):
+    """collate_fn's layout: int64 [B, width] = the ascending positions < rowlen[b] with mask False, then -1; (ids, kept counts)."""
+    B, S = mask.shape
+    pos = torch.arange(S, device=mask.device).expand(B, S)
+    kept = ~mask & (pos < rowlen.view(B, 1))
+    first = torch.sort(torch.where(kept, pos, pos + S), dim=1).values
+    count = kept.sum(1)
+    if width > S:
+        first = torch.cat([first, first.new_zeros(B, width - S)], dim=1)
+    col = torch.arange(width, device=mask.device).expand(B, width)
+    return torch.where(col < count.view(B, 1), first[:, :width], torch.full((), -1, dtype=torch.int64, device=mask.device)), count
+
+
+def _mask_keys(keys, name, shape=None):
+    if not torch.is_tensor(keys) or keys.dim() != 2 or keys.dtype != torch.int32 or (shape is not None and tuple(keys.shape) != tuple(shape)):
+        raise ValueError("%s must be an int32 tensor [B, n]%s" % (name, "" if shape is None else " of shape %s" % (tuple(shape),)))
+    if keys.shape[1] > hip.MASK_MAX_ITEMS:
+        raise ValueError("%s: %d items per row, at most %d" % (name, keys.shape[1], hip.MASK_MAX_ITEMS))
+    return keys.contiguous()
+
+
+def patch_masks(keys_a, keys_b, m1, extra):
+    """The image masks of image_text_pretrain_dataset.py:85-104 for a batch: (image_mask bool [B, N + 1], image_ids int64 [B, N + 1 - m1],
+    vl_mask bool [B, N + 1], vl_ids int64 [B, m1 - extra + 1]).  keys_a, keys_b: int32 [B, N] >= 0.  image mask = select(all, m1, keys_a)
+    (randperm(N)[:m1]); vl mask = (not image-masked) U select(image-masked, extra, keys_b).  Position 0 (CLS) is never masked, patch j is
+    position j + 1.  m1 = int(N * image_mask_ratio), extra = int(N * vl_image_mask_ratio) - (N - m1): host ints.  ValueError unless
+    0 <= extra <= m1 <= N <= 4096.  CUDA keys: op_mask_patches, one launch; CPU keys: the same rule in torch, the same bits."""
+    keys_a = _mask_keys(keys_a, "patch_masks: keys_a")
+    keys_b = _mask_keys(keys_b, "patch_masks: keys_b", keys_a.shape)
+    B, N = keys_a.shape
+    m1, extra = int(m1), int(extra)
+    if N < 1 or not 0 <= m1 <= N or not 0 <= extra <= m1:
+        raise ValueError("patch_masks: need 0 <= extra <= m1 <= N and N >= 1, got extra %d, m1 %d, N %d" % (extra, m1, N))
+    if keys_a.is_cuda:
+        return hip.mask_patches(keys_a, m1, keys_b, extra)
+    every = torch.ones(B, N, dtype=torch.bool)
+    m = _select_rank(every, keys_a) < m1
+    vl = ~m | (_select_rank(m, keys_b) < extra)
+    cls = torch.zeros(B, 1, dtype=torch.bool)
+    m, vl = torch.cat([cls, m], 1), torch.cat([cls, vl], 1)
+    rowlen = torch.full((B,), N + 1)
+    return m, _preserve_ids(m, rowlen, N + 1 - m1)[0], vl, _preserve_ids(vl, rowlen, m1 - extra + 1)[0]
+
+
+def word_masks(src_tokens, word_start, keys_a, p, keys_b=None, vl_ratio=None, pad=1, width=None):
+    """Whole-word text masks of a batch (add_whole_word_mask, image_text_pretrain_dataset.py:121-139, and the vl text mask of :73-77):
+    (mask bool [B, L + 1], ids int64 [B, width], vl_mask, vl_ids (None without keys_b), overflow: a 0-dim bool tensor on the batch's device).
+    src_tokens: int64 [B, L] as the model receives it: the caption's tokens, eos, then `pad`; n = non-pad count - 1 tokens, token t at
+    position t + 1; position 0 (CLS), eos and pads are never masked.  word_start: uint8 [vocab] on the same device (whole_word_table).
+    With W word starts among the row's tokens, k = ceil(float32(W) * p) starts are select(starts, k, keys_a), each masked with the tokens
+    after it up to the next start or the caption's end.  vl mask (keys_b and vl_ratio given) = select(tokens not masked,
+    int(n * vl_ratio), keys_b); when fewer tokens are unmasked, masked tokens follow in index order (the reference's argsort leaves that
+    case open).  A row with n == 0 or W == 0 gets no masked token, where the reference asserts.
+    ids: the ascending positions 0 ... n + 1 with mask False, then -1.  width=None takes the batch maximum of each mask, which costs ONE
+    device-to-host read; an int, or a pair for (ids, vl_ids), is an upper bound and costs no synchronisation: a row that keeps more
+    positions has its ids truncated to the first `width`, and `overflow` is True.
+    CUDA tokens: op_mask_words, one launch; CPU tokens: the same rule in torch, the same bits."""
+    if not torch.is_tensor(src_tokens) or src_tokens.dim() != 2 or src_tokens.dtype != torch.int64:
+        raise ValueError("word_masks: src_tokens must be an int64 tensor [B, L]")
+    B, L = src_tokens.shape
+    if not 1 <= L <= hip.MASK_MAX_ITEMS:
+        raise ValueError("word_masks: L = %d tokens per row, need 1 ... %d" % (L, hip.MASK_MAX_ITEMS))
+    keys_a = _mask_keys(keys_a, "word_masks: keys_a", (B, L))
+    vl = keys_b is not None
+    if vl != (vl_ratio is not None):
+        raise ValueError("word_masks: keys_b and vl_ratio go together")
+    if vl:
+        keys_b = _mask_keys(keys_b, "word_masks: keys_b", (B, L))
+    if not 0.0 <= p <= 1.0 or (vl and not 0.0 <= vl_ratio <= 1.0):
+        raise ValueError("word_masks: mask ratios must lie in [0, 1]")
+    if word_start.dtype != torch.uint8 or word_start.dim() != 1 or word_start.device != src_tokens.device:
+        raise ValueError("word_masks: word_start must be a uint8 [vocab] tensor on the tokens' device")
+    widths = (None, None) if width is None else (tuple(width) if isinstance(width, (tuple, list)) else (width, width))
+    if width is not None and not all(0 <= int(w) <= L + 1 for w in widths):
+        raise ValueError("word_masks: width must lie in [0, L + 1]")
+    dev = src_tokens.device
+    if src_tokens.is_cuda:
+        if L > 1 and src_tokens.stride(1) != 1:
+            src_tokens = src_tokens.contiguous()
+        m, ids, vm, vids, counts = hip.mask_words(src_tokens, word_start.contiguous(), keys_a, p, keys_b, vl_ratio if vl else 0.0, pad,
+                                                  widths[0], widths[1])
+        if not vl:
+            counts = counts[:1]
+    else:
+        nonpad = src_tokens.ne(pad).sum(1)
+        n = (nonpad - 1).clamp(min=0)
+        in_cap = torch.arange(L).expand(B, L) < n.view(B, 1)
+        vocab = word_start.numel()
+        ws = word_start[src_tokens.clamp(0, vocab - 1)].ne(0) & in_cap & (src_tokens >= 0) & (src_tokens < vocab)
+        W = ws.sum(1)
+        k = torch.ceil(W.float() * p).long().clamp(max=W)  # torch's own rounding of is_word_start.float().sum() * p
+        chosen = ws & (_select_rank(ws, keys_a, in_cap) < k.view(B, 1))
+        wid = torch.cumsum(ws.long(), 1)  # the word a token belongs to; 0 before the first start
+        hit = torch.zeros(B, L + 1, dtype=torch.int64).scatter_add_(1, wid * chosen, chosen.long())
+        hit[:, 0] = 0
+        tm = hit.gather(1, wid).ne(0) & in_cap
+        cls = torch.zeros(B, 1, dtype=torch.bool)
+        m = torch.cat([cls, tm], 1)
+        rowlen = nonpad + 1
+        ids, c0 = _preserve_ids(m, rowlen, L + 1 if widths[0] is None else int(widths[0]))
+        vm = vids = None
+        counts = c0.view(1, B)
+        if vl:
+            k2 = (n.double() * vl_ratio).long().clamp(max=n)
+            vm = torch.cat([cls, in_cap & (_select_rank(in_cap & ~tm, keys_b, in_cap) < k2.view(B, 1))], 1)
+            vids, c1 = _preserve_ids(vm, rowlen, L + 1 if widths[1] is None else int(widths[1]))
+            counts = torch.stack([c0, c1])
+    if width is None:
+        most = counts.max(1).values.tolist() if B else [0] * counts.shape[0]  # the one device-to-host read
+        ids = ids[:, :most[0]].contiguous()
+        if vl:
+            vids = vids[:, :most[1]].contiguous()
+        overflow = torch.zeros((), dtype=torch.bool, device=dev)
+    else:
+        lim = torch.tensor([int(w) for w in widths[:counts.shape[0]]], device=dev).view(-1, 1)
+        overflow = (counts > lim).any()
+    return m, ids, vm, vids, overflow
+
+
+def block_counts(frames, mask_prob, mask_length, mask_prob_adjust=0.0):
+    """(K, target) of compute_block_mask_1d for a clip of `frames` frames, in Python double arithmetic exactly as data_utils.py:153-157 and
+    :191 write them: K = int(T * ((p + adjust) / length)) centres, target = int(T * p) masked frames."""
+    T = int(frames)
+    return int(T * ((mask_prob + mask_prob_adjust) / mask_length)), int(T * mask_prob)
+
+
+def block_masks(frames, centers, keys, mask_prob, mask_length, mask_prob_adjust=0.0, width=None, inverse_mask=False, require_same_masks=True,
+                expand_adjcent=False, mask_dropout=0.0, non_overlapping=False):
+    """compute_block_mask_1d (one_peace/utils/data_utils.py:110-231) on its default path, the one the audio dataset calls, for a batch of
+    clips of different lengths: (mask bool [B, Tmax + 1], ids int64 [B, width]).  frames: a host sequence of B frame counts T_b;
+    centers: int32 [B, Kmax] in [0, T_b), row b's first K_b are used; keys: int32 [B, Tmax] >= 0; (K_b, target_b) = block_counts(T_b, ...).
+    Frames clamp(c + i - length // 2, 0, T_b - 1), i < length, are masked for every centre; with n masked frames, n > target unmasks
+    select(masked, n - target, keys) and n < target masks select(unmasked, target - n, keys).  Frame j is position j + 1, position 0
+    (CLS) is never masked, rows are padded to the batch width with False.  width=None: max_b(T_b + 1 - target_b), known on the host.
+    The other paths of the reference (non_overlapping, expand_adjcent, mask_dropout, inverse_mask, require_same_masks=False) raise
+    NotImplementedError.  CUDA keys: op_mask_blocks, one launch; CPU keys: the same rule in torch, the same bits."""
+    import numpy as np
+    if inverse_mask or not require_same_masks or expand_adjcent or mask_dropout or non_overlapping:
+        raise NotImplementedError("block_masks: only compute_block_mask_1d's default path (overlapping blocks, require_same_masks) is provided")
+    keys = _mask_keys(keys, "block_masks: keys")
+    B, Tmax = keys.shape
+    if not torch.is_tensor(centers) or centers.dim() != 2 or centers.dtype != torch.int32 or centers.shape[0] != B or centers.device != keys.device:
+        raise ValueError("block_masks: centers must be an int32 tensor [B, Kmax] on the keys' device")
+    centers = centers.contiguous()
+    Kmax, length = centers.shape[1], int(mask_length)
+    frames = [int(t) for t in frames]
+    if len(frames) != B or Tmax < 1 or not 1 <= length <= hip.MASK_MAX_ITEMS or Kmax > hip.MASK_MAX_ITEMS or not 0.0 <= mask_prob <= 1.0:
+        raise ValueError("block_masks: need B frame counts, 1 <= Tmax, 1 <= mask_length <= %d, Kmax <= %d, 0 <= mask_prob <= 1" % (
+            hip.MASK_MAX_ITEMS, hip.MASK_MAX_ITEMS))
+    rows = np.zeros((B, 3), dtype=np.int32)
+    for b, T in enumerate(frames):
+        K, target = block_counts(T, mask_prob, length, mask_prob_adjust)
+        if not 0 <= T <= Tmax or not 0 <= K <= Kmax:
+            raise ValueError("block_masks: clip %d: T = %d, K = %d, need 0 <= T <= Tmax = %d and 0 <= K <= Kmax = %d" % (b, T, K, Tmax, Kmax))
+        rows[b] = (T, K, target)
+    need = int((rows[:, 0] + 1 - rows[:, 2]).max()) if B else 1
+    width = need if width is None else int(width)
+    if not need <= width <= Tmax + 1:
+        raise ValueError("block_masks: width = %d, need %d ... %d" % (width, need, Tmax + 1))
+    if keys.is_cuda:
+        return hip.mask_blocks(rows, centers, keys, length, width)
+    T, K, target = (torch.from_numpy(rows[:, i].astype(np.int64)).view(B, 1) for i in range(3))
+    f = torch.zeros(B, Tmax + 1, dtype=torch.bool)
+    used = torch.arange(Kmax).expand(B, Kmax) < K
+    for i in range(length):
+        q = torch.minimum((centers.long() + (i - length // 2)).clamp(min=0), (T - 1).clamp(min=0))
+        f.scatter_(1, torch.where(used, q, torch.full((), Tmax, dtype=torch.int64)), torch.ones(B, Kmax, dtype=torch.bool))
+    f = f[:, :Tmax]
+    in_row = torch.arange(Tmax).expand(B, Tmax) < T
+    n = f.sum(1, keepdim=True)
+    drop = n > target
+    change = (f == drop) & in_row & (_select_rank((f == drop) & in_row, keys, in_row) < (n - target).abs())
+    f = torch.where(change, ~drop, f)
+    m = torch.cat([torch.zeros(B, 1, dtype=torch.bool), f], 1)
+    return m, _preserve_ids(m, T.view(B) + 1, width)[0]
