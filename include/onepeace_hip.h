@@ -786,6 +786,35 @@ int op_attn_pool_bwd(const void* dout, const void* k, const void* v, int64_t ld,
                      void* dk, void* dv, int64_t ldg, int64_t batch_stride_g, float* dq_part, int64_t B, int64_t S, int64_t heads,
                      int64_t hd, void* stream);
 
+/* ---- mean-pool head of the vision-branch classifier (csrc/tokenpool.hip) -------------------------------------------------------------
+ * Additive: op_abi_version() stays 10, no existing entry point changed.
+ * op_token_mean_ln_fwd replaces one_peace_vision/classification/models_vit.py:431-434 up to the head's Linear (OnePeaceViT.forward_head
+ * with global_pool: x[:, 1:, :].mean(dim=1), then fc_norm); op_token_mean_ln_bwd replaces the autograd backward of those two lines (the
+ * expanded mean, the zero-filled slice gradient, the LayerNorm backward).  The Linear of :434 stays a GEMM of its own.
+ * x: bf16, element (b, s, h) at b * batch_stride + s * ld + h (strides in elements): a view of a larger buffer needs no copy.  Row s = 0
+ * (CLS) is NEVER read.  w, b: bf16 [H], either may be NULL (1 resp. 0).  y: bf16 [B, H], dense.  pooled: fp32 [B, H]; mean, rstd: fp32
+ * [B]: kept for the backward.
+ *   pooled  = (sum_{s >= 1} x[b, s, :]) / (S - 1) in fp32 -- a DEVIATION from the reference, which rounds the mean to bf16 before the norm
+ *   mean, rstd = the statistics of pooled[b, :] over H in fp32 (two passes; rstd = 1 / sqrt(var + eps), var the biased variance)
+ *   y       = (pooled - mean) * rstd * w + b, rounded to bf16 once (to nearest even)
+ * part: fp32 workspace of the caller, B * OP_TOKEN_POOL_MAX_SPLITS * H elements.  The tokens of a sample are summed in P splits (P a
+ * function of S alone, at most OP_TOKEN_POOL_MAX_SPLITS) by separate workgroups into part [B, P, H]; the pass that normalises adds the
+ * P partials in index order.  Its contents mean nothing after the call.
+ * op_token_mean_ln_bwd, with pooled, mean, rstd as stored, xhat = (pooled - mean) * rstd, g = dy * w, c1 = mean_h(g), c2 = mean_h(g xhat):
+ *   dpool = rstd * (g - c1 - xhat * c2) in fp32;   dx[b, s, :] = bf16(dpool[b, :] / (S - 1)) for every s >= 1, +0 for s = 0.
+ * dy: bf16 [B, H], dense.  dx: bf16 with its own strides ldg / batch_stride_g; EVERY element of [B, S, H] is written (the value is
+ * converted once per column and stored down the rows).  dw_part, db_part: fp32 [H], the sums over b, in index order, of dy * xhat and
+ * of dy; WRITTEN, not accumulated; either may be NULL.  dx may be NULL too (the parts alone; its strides are still checked), not all three.
+ * Every sum runs in a fixed order and there are no atomics: two runs give the same bits, and the results of sample b do not depend on B.
+ * Limits (OP_EINVAL with a message otherwise, nothing launched): H % 8 == 0 and 8 <= H <= 8192; 2 <= S <= 65536; B <= 2^20; ld, ldg >= H;
+ * ld, ldg and the batch strides non-negative multiples of 8; batch_stride_g >= (S - 1) * ldg + H when B > 1; every pointer but mean and
+ * rstd (4 bytes) aligned to 16 bytes; eps >= 0.  B == 0 returns without a launch.  Nothing is allocated or synchronised. */
+#define OP_TOKEN_POOL_MAX_SPLITS 16
+int op_token_mean_ln_fwd(const void* x, int64_t ld, int64_t batch_stride, const void* w, const void* b, float eps, void* y,
+                         float* pooled, float* mean, float* rstd, float* part, int64_t B, int64_t S, int64_t H, void* stream);
+int op_token_mean_ln_bwd(const void* dy, const float* pooled, const void* w, const float* mean, const float* rstd, void* dx, int64_t ldg,
+                         int64_t batch_stride_g, float* dw_part, float* db_part, int64_t B, int64_t S, int64_t H, void* stream);
+
 /* ---- pretraining masks: whole words, image patches, audio blocks (csrc/masks.hip) --------------------------------------------------
  * Additive: op_abi_version() stays 10, no existing entry point changed.
  * Every random choice is select(candidates, k, keys): the k items first in the order (key descending, index ascending) over the

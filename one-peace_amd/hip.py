@@ -119,6 +119,8 @@ SIGNATURES = {
     "op_box_loss": (c_int, [P, c_int, P, I64, c_float, P, P, P]),
     "op_attn_pool_fwd": (c_int, [P, P, I64, I64, P, P, I64, P, P, I64, I64, I64, I64, P]),
     "op_attn_pool_bwd": (c_int, [P, P, P, I64, I64, P, P, P, P, I64, I64, P, I64, I64, I64, I64, P]),
+    "op_token_mean_ln_fwd": (c_int, [P, I64, I64, P, P, c_float, P, P, P, P, P, I64, I64, I64, P]),
+    "op_token_mean_ln_bwd": (c_int, [P, P, P, P, P, P, I64, I64, P, P, I64, I64, I64, P]),
     "op_mask_patches": (c_int, [P, P, I64, I64, I64, I64, P, P, P, P, P]),
     "op_mask_words": (c_int, [P, I64, I64, I64, I64, P, I64, P, P, c_float, c_double, P, P, I64, P, P, I64, P, P]),
     "op_mask_blocks": (c_int, [P, P, P, I64, P, I64, I64, I64, P, P, I64, P]),
@@ -1770,6 +1772,88 @@ def attn_pool_bwd(dout, k, v, q, p, dk=None, dv=None, dq_part=None):
     _check(lib().op_attn_pool_bwd(ptr(dout), ptr(k), ptr(v), ld, bs, ptr(q), ptr(p), ptr(dk), ptr(dv), ldg, bsg, ptr(dq_part), B, S, heads,
                                   hd, stream()), "op_attn_pool_bwd")
     return dk, dv, dq_part
+
+
+TOKEN_POOL_MAX_SPLITS = 16  # include/onepeace_hip.h: OP_TOKEN_POOL_MAX_SPLITS (csrc/tokenpool.hip: TP_MAX_SPLITS)
+TOKEN_POOL_MAX_B = 1 << 20
+
+
+def _token_pool_strides(x):
+    """(ld, batch_stride) of a [B, S, H] view as the entries take them (torch gives a size-1 dimension any stride)."""
+    B, S, H = x.shape
+    return x.stride(1), (x.stride(0) if B > 1 else 0)
+
+
+def token_pool_supported(x, w=None, b=None):
+    """The limits of op_token_mean_ln_fwd / _bwd for x [B, S, H] (any batch / row strides the kernels take), w and b [H] or None."""
+    if x.dim() != 3 or x.dtype != torch.bfloat16 or not x.is_cuda:
+        return False
+    B, S, H = x.shape
+    for t in (w, b):
+        if t is not None and not (t.is_cuda and t.dtype == torch.bfloat16 and tuple(t.shape) == (H,) and t.is_contiguous()
+                                  and t.data_ptr() % 16 == 0):
+            return False
+    ld, bs = _token_pool_strides(x)
+    return (H % 8 == 0 and 8 <= H <= 8192 and 2 <= S <= 65536 and 1 <= B <= TOKEN_POOL_MAX_B and x.stride(2) == 1 and ld % 8 == 0
+            and ld >= H and bs % 8 == 0 and bs >= 0 and x.data_ptr() % 16 == 0)
+
+
+def _token_pool_view(t, name):
+    if not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 3 or t.stride(2) != 1:
+        raise RuntimeError("token_mean_ln: %s must be a bf16 CUDA(HIP) tensor [B, S, H] with unit column stride" % name)
+    return tuple(t.shape) + _token_pool_strides(t)
+
+
+def token_mean_ln_fwd(x, w, b, eps=1e-5, y=None, pooled=None, mean=None, rstd=None):
+    """op_token_mean_ln_fwd: x bf16 [B, S, H] (own strides, unit column stride), w / b bf16 [H] or None.  Returns (y bf16 [B, H],
+    pooled fp32 [B, H], mean fp32 [B], rstd fp32 [B]); the split partials live in the grow-only workspace of this stream."""
+    B, S, H, ld, bs = _token_pool_view(x, "x")
+    _req(w, "w", torch.bfloat16)
+    _req(b, "b", torch.bfloat16)
+    dev = x.device
+    if y is None:
+        y = torch.empty(B, H, dtype=torch.bfloat16, device=dev)
+    if pooled is None:
+        pooled = torch.empty(B, H, dtype=torch.float32, device=dev)
+    if mean is None:
+        mean = torch.empty(B, dtype=torch.float32, device=dev)
+    if rstd is None:
+        rstd = torch.empty(B, dtype=torch.float32, device=dev)
+    for t, name, dt, shape in ((y, "y", torch.bfloat16, (B, H)), (pooled, "pooled", torch.float32, (B, H)),
+                               (mean, "mean", torch.float32, (B,)), (rstd, "rstd", torch.float32, (B,))):
+        _req(t, name, dt)
+        assert tuple(t.shape) == shape, "%s must be %s" % (name, shape)
+    part = workspace(4 * B * TOKEN_POOL_MAX_SPLITS * H, dev, "token_pool")
+    _check(lib().op_token_mean_ln_fwd(ptr(x), ld, bs, ptr(w), ptr(b), eps, ptr(y), ptr(pooled), ptr(mean), ptr(rstd), ptr(part), B, S, H,
+                                      stream()), "op_token_mean_ln_fwd")
+    return y, pooled, mean, rstd
+
+
+def token_mean_ln_bwd(dy, pooled, w, mean, rstd, S, dx=None, want_parts=True, dw_part=None, db_part=None, want_dx=True):
+    """op_token_mean_ln_bwd: returns (dx bf16 [B, S, H], dw_part, db_part fp32 [H] or None).  dx may be given as a view with its own
+    strides; every element of [B, S, H] is written, row 0 with zeros.  dw_part / db_part may be given (contiguous fp32 [H], e.g. the two
+    rows of one [2, H] buffer; either may stay None); with neither given, want_parts says whether the pair is allocated here.
+    want_dx=False (and no dx given): the parts alone, dx is neither allocated nor written and None is returned for it."""
+    _req(dy, "dy", torch.bfloat16)
+    _req(pooled, "pooled", torch.float32)
+    _req(mean, "mean", torch.float32)
+    _req(rstd, "rstd", torch.float32)
+    _req(w, "w", torch.bfloat16)
+    B, H = dy.shape
+    assert tuple(pooled.shape) == (B, H) and mean.numel() == B and rstd.numel() == B
+    if dx is None and want_dx:
+        dx = torch.empty(B, S, H, dtype=torch.bfloat16, device=dy.device)
+    ldg, bsg = H, S * H
+    if dx is not None:
+        Bx, Sx, Hx, ldg, bsg = _token_pool_view(dx, "dx")
+        assert (Bx, Sx, Hx) == (B, S, H), "dx must be [B, S, H]"
+    if want_parts and dw_part is None and db_part is None:
+        dw_part, db_part = torch.empty(2, H, dtype=torch.float32, device=dy.device).unbind(0)
+    _req(dw_part, "dw_part", torch.float32)
+    _req(db_part, "db_part", torch.float32)
+    _check(lib().op_token_mean_ln_bwd(ptr(dy), ptr(pooled), ptr(w), ptr(mean), ptr(rstd), ptr(dx), ldg, bsg, ptr(dw_part), ptr(db_part),
+                                      B, S, H, stream()), "op_token_mean_ln_bwd")
+    return dx, dw_part, db_part
 
 
 MASK_MAX_ITEMS = 4096  # csrc/masks.hip: MK_MAX, the items (positions without CLS) of one row

@@ -2509,6 +2509,63 @@ def attention_pool(k, v, q, key_padding_mask=None):
 
 
 # --------------------------------------------------------------------------------------------------------------
+# vision-branch classifier head: mean of the patch tokens + fc_norm (one_peace_vision/classification/models_vit.py:431-434;
+# csrc/tokenpool.hip)
+# --------------------------------------------------------------------------------------------------------------
+def token_mean_norm_torch(x, weight, bias, eps=1e-5):
+    """models_vit.py:432-433 with global_pool: the same torch ops in the same order and dtypes.  x: [B, S, H], row 0 is CLS."""
+    x = x[:, 1:, :].mean(dim=1)
+    return F.layer_norm(x, (x.shape[-1],), weight, bias, eps)
+
+
+class TokenMeanNormFn(torch.autograd.Function):
+    """op_token_mean_ln_fwd / op_token_mean_ln_bwd; the fp32 mean row and its statistics are kept for the backward, which writes the
+    gradient of the whole activation tensor once (CLS row zero).  The [H] parts are cast to the parameters' dtype."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        y, pooled, mean, rstd = hip.token_mean_ln_fwd(x, weight, bias, eps)
+        ctx.save_for_backward(pooled, weight, mean, rstd)
+        ctx.tokens, ctx.has_bias = x.shape[1], bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        pooled, weight, mean, rstd = ctx.saved_tensors
+        need_w = weight is not None and ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        need_x = ctx.needs_input_grad[0]
+        if not (need_x or need_w or need_b):
+            return None, None, None, None
+        dy = dy.contiguous()
+        if dy.data_ptr() % 16:  # (a view that starts inside a row of a larger buffer: the entry wants 16-byte alignment)
+            dy = dy.clone()
+        dw = db = parts = None
+        if need_w or need_b:
+            parts = torch.empty(2, dy.shape[1], dtype=torch.float32, device=dy.device)
+        dx, _, _ = hip.token_mean_ln_bwd(dy, pooled, weight, mean, rstd, ctx.tokens, want_dx=need_x, want_parts=False,
+                                         dw_part=parts[0] if need_w else None, db_part=parts[1] if need_b else None)
+        if parts is not None:
+            dw, db = parts.to(dy.dtype).unbind(0)  # the parameters' dtype: bf16 on this route; one cast for the pair
+        return dx, dw if need_w else None, db if need_b else None, None
+
+
+def token_mean_norm(x, weight, bias, eps=1e-5):
+    """[B, H] = LayerNorm(mean over the tokens 1 ... S - 1 of x [B, S, H]; weight, bias, eps): OnePeaceViT.forward_head before its Linear.
+    bf16 CUDA tensors inside the kernels' limits (hip.token_pool_supported: H % 8 == 0, H <= 8192, 2 <= S <= 65536, strides multiples
+    of 8) run op_token_mean_ln_fwd / _bwd, which never read the CLS row and keep the mean in fp32 between the two steps (the reference
+    rounds it to bf16 first); everything else -- CPU, fp32, fp16, odd H, unaligned views -- runs token_mean_norm_torch."""
+    if x.dim() != 3 or x.shape[1] < 2:
+        raise ValueError("token_mean_norm: x %s must be [B, S, H] with S >= 2 (CLS and at least one token)" % (tuple(x.shape),))
+    if hip_eligible(x) and all(t is None or hip_eligible(t) for t in (weight, bias)):
+        w = weight.contiguous() if weight is not None else None
+        b = bias.contiguous() if bias is not None else None
+        if hip.token_pool_supported(x, w, b):
+            return TokenMeanNormFn.apply(x, w, b, float(eps))
+    return token_mean_norm_torch(x, weight, bias, eps)
+
+
+# --------------------------------------------------------------------------------------------------------------
 # pretraining masks (csrc/masks.hip; pretrain_masks.py draws the keys): every random choice is select(candidates, k, keys)
 # --------------------------------------------------------------------------------------------------------------
 def _select_rank(cand, keys, in_row=None):
