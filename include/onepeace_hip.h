@@ -815,6 +815,35 @@ int op_token_mean_ln_fwd(const void* x, int64_t ld, int64_t batch_stride, const 
 int op_token_mean_ln_bwd(const void* dy, const float* pooled, const void* w, const float* mean, const float* rstd, void* dx, int64_t ldg,
                          int64_t batch_stride_g, float* dw_part, float* db_part, int64_t B, int64_t S, int64_t H, void* stream);
 
+/* ---- temporal attention of the video branch (csrc/frameattn.hip) ---------------------------------------------------------------------
+ * Additive: op_abi_version() stays 10, no existing entry point changed.
+ * op_attn_frames_fwd replaces one_peace_vision/video/mmaction_custom/models/backbones/onepeace.py:234-247 (MultiheadAttention.forward
+ * between its projections and the sub-LayerNorm: the head views, q * scaling, bmm, softmax, bmm, the transpose back) as called from
+ * :331-337, INCLUDING the two rearranges 'n (b t) d -> t (b n) d' (:331) and 't (b n) d -> n (b t) d' (:337): self-attention over the T
+ * frames of a clip, one sequence per (video b, token position n, head h), no bias, no mask, no dropout.  op_attn_frames_bwd replaces the
+ * autograd backward of those lines.  The projections, the LayerNorms and the adapters of :334-336 are row-wise and stay what they are.
+ * Layout: every tensor is bf16; element (b, t, n, h, d) lies at ((b * T + t) * N + n) * ld + h * hd + d (strides in elements): the
+ * project's batch-major rows of B * T frames with N tokens each.  q, k, v share ld: the three column blocks of one packed [R, 3 H]
+ * projection output (R = B * T * N, H = heads * hd) serve without a copy.  out and dout use the same row order with the stride ldo,
+ * dq / dk / dv with ldg: they may be the column blocks of one packed [R, 3 H] gradient matrix.  Columns beyond heads * hd of a row are
+ * neither read nor written.
+ *   forward   s = scale * (q_t . k_t') in fp32 (a 64-term dot, then the factor);  p = softmax over t' in fp32, the maximum subtracted
+ *             (expf);  out_t = (sum_t' e_t' v_t') / (sum_t' e_t') in fp32, rounded to bf16 once (to nearest even).
+ *             DEVIATION from the reference's bf16 run: s and p are never rounded to bf16 (the reference's bmm outputs are), and q is not
+ *             rounded after the scaling (the reference's `q *= self.scaling` is): more accurate, not bit-compatible.
+ *   backward  p is RECOMPUTED from q and k: nothing but q, k, v is kept from the forward, `out` is not an argument.  dp = dout_t . v_t',
+ *             c = sum_t' p dp,  ds = p (dp - c),  dv_t' = sum_t p dout_t,  dq_t = scale * sum_t' ds k_t',  dk_t' = scale * sum_t ds q_t;
+ *             each rounded to bf16 once.  EVERY element of [R, heads * hd] of dq, dk and dv is written.
+ * No atomics, every sum in a fixed order inside one lane: two runs give the same bits, and the bits of sequence (b, n, h) depend on its
+ * own T rows, T and scale alone -- not on B, N or heads.
+ * Limits (OP_EINVAL with a message otherwise, nothing launched; checked before the device is touched): hd == 64; 1 <= T <= 32;
+ * N, heads >= 1; B >= 0; ld, ldo, ldg multiples of 8 and >= heads * hd; every pointer non-null and aligned to 16 bytes;
+ * B * N * heads < 2^31.  Offsets are 64-bit.  B == 0 returns without a launch.  Nothing is allocated or synchronised. */
+int op_attn_frames_fwd(const void* q, const void* k, const void* v, int64_t ld, void* out, int64_t ldo, int64_t B, int64_t T, int64_t N,
+                       int64_t heads, int64_t hd, float scale, void* stream);
+int op_attn_frames_bwd(const void* q, const void* k, const void* v, int64_t ld, const void* dout, int64_t ldo, void* dq, void* dk, void* dv,
+                       int64_t ldg, int64_t B, int64_t T, int64_t N, int64_t heads, int64_t hd, float scale, void* stream);
+
 /* ---- pretraining masks: whole words, image patches, audio blocks (csrc/masks.hip) --------------------------------------------------
  * Additive: op_abi_version() stays 10, no existing entry point changed.
  * Every random choice is select(candidates, k, keys): the k items first in the order (key descending, index ascending) over the

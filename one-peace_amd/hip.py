@@ -121,6 +121,8 @@ SIGNATURES = {
     "op_attn_pool_bwd": (c_int, [P, P, P, I64, I64, P, P, P, P, I64, I64, P, I64, I64, I64, I64, P]),
     "op_token_mean_ln_fwd": (c_int, [P, I64, I64, P, P, c_float, P, P, P, P, P, I64, I64, I64, P]),
     "op_token_mean_ln_bwd": (c_int, [P, P, P, P, P, P, I64, I64, P, P, I64, I64, I64, P]),
+    "op_attn_frames_fwd": (c_int, [P, P, P, I64, P, I64, I64, I64, I64, I64, I64, c_float, P]),
+    "op_attn_frames_bwd": (c_int, [P, P, P, I64, P, I64, P, P, P, I64, I64, I64, I64, I64, I64, c_float, P]),
     "op_mask_patches": (c_int, [P, P, I64, I64, I64, I64, P, P, P, P, P]),
     "op_mask_words": (c_int, [P, I64, I64, I64, I64, P, I64, P, P, c_float, c_double, P, P, I64, P, P, I64, P, P]),
     "op_mask_blocks": (c_int, [P, P, P, I64, P, I64, I64, I64, P, P, I64, P]),
@@ -1854,6 +1856,60 @@ def token_mean_ln_bwd(dy, pooled, w, mean, rstd, S, dx=None, want_parts=True, dw
     _check(lib().op_token_mean_ln_bwd(ptr(dy), ptr(pooled), ptr(w), ptr(mean), ptr(rstd), ptr(dx), ldg, bsg, ptr(dw_part), ptr(db_part),
                                       B, S, H, stream()), "op_token_mean_ln_bwd")
     return dx, dw_part, db_part
+
+
+ATTN_FRAMES_MAX_T = 32  # csrc/frameattn.hip: one lane per (head, frame), at most 32 frames
+
+
+def _frames_cols(t, H, name):
+    """Row stride of a [R, H] bf16 view as op_attn_frames_* take it (a column block of a wider matrix is fine)."""
+    if not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape[1] != H or (H > 1 and t.stride(1) != 1):
+        raise RuntimeError("attn_frames: %s must be a bf16 CUDA(HIP) tensor [R, heads * 64] with unit column stride" % name)
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), H)
+
+
+def attn_frames_supported(qkv, B, T, N, heads, hd):
+    """The limits of op_attn_frames_fwd / _bwd for a packed q|k|v matrix [B * T * N, 3 * heads * hd]."""
+    H = heads * hd
+    if qkv.dim() != 2 or not qkv.is_cuda or qkv.dtype != torch.bfloat16 or tuple(qkv.shape) != (B * T * N, 3 * H):
+        return False
+    ld = qkv.stride(0) if qkv.shape[0] > 1 else max(qkv.stride(0), 3 * H)
+    return (hd == 64 and 1 <= T <= ATTN_FRAMES_MAX_T and N >= 1 and heads >= 1 and B >= 1 and B * N * heads < 2 ** 31
+            and qkv.stride(1) == 1 and ld % 8 == 0 and ld >= 3 * H and qkv.data_ptr() % 16 == 0)
+
+
+def attn_frames_fwd(q, k, v, B, T, N, heads, scale, out=None):
+    """op_attn_frames_fwd: q, k, v bf16 [B * T * N, heads * 64] views sharing one row stride (the column blocks of a packed projection
+    output), rows ordered (b, t, n).  Returns out bf16 [B * T * N, heads * 64] (own row stride when given)."""
+    H = heads * 64
+    ld = _frames_cols(q, H, "q")
+    if _frames_cols(k, H, "k") != ld or _frames_cols(v, H, "v") != ld or not (q.shape[0] == k.shape[0] == v.shape[0] == B * T * N):
+        raise RuntimeError("attn_frames_fwd: q, k, v must share the row stride and have B * T * N = %d rows" % (B * T * N))
+    if out is None:
+        out = torch.empty(B * T * N, H, dtype=torch.bfloat16, device=q.device)
+    ldo = _frames_cols(out, H, "out")
+    assert out.shape[0] == B * T * N
+    _check(lib().op_attn_frames_fwd(ptr(q), ptr(k), ptr(v), ld, ptr(out), ldo, B, T, N, heads, 64, scale, stream()), "op_attn_frames_fwd")
+    return out
+
+
+def attn_frames_bwd(q, k, v, dout, B, T, N, heads, scale, dqkv=None):
+    """op_attn_frames_bwd: returns dqkv bf16 [B * T * N, 3 H], dq | dk | dv packed like a fused projection output (every element
+    written).  p is recomputed from q and k: the forward's output is not needed."""
+    H = heads * 64
+    ld = _frames_cols(q, H, "q")
+    if _frames_cols(k, H, "k") != ld or _frames_cols(v, H, "v") != ld or not (q.shape[0] == k.shape[0] == v.shape[0] == B * T * N):
+        raise RuntimeError("attn_frames_bwd: q, k, v must share the row stride and have B * T * N = %d rows" % (B * T * N))
+    ldo = _frames_cols(dout, H, "dout")
+    assert dout.shape[0] == B * T * N
+    if dqkv is None:
+        dqkv = torch.empty(B * T * N, 3 * H, dtype=torch.bfloat16, device=q.device)
+    assert dqkv.dim() == 2 and tuple(dqkv.shape) == (B * T * N, 3 * H)
+    dq, dk, dv = dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:]
+    ldg = _frames_cols(dq, H, "dq")
+    _check(lib().op_attn_frames_bwd(ptr(q), ptr(k), ptr(v), ld, ptr(dout), ldo, ptr(dq), ptr(dk), ptr(dv), ldg, B, T, N, heads, 64, scale,
+                                    stream()), "op_attn_frames_bwd")
+    return dqkv
 
 
 MASK_MAX_ITEMS = 4096  # csrc/masks.hip: MK_MAX, the items (positions without CLS) of one row

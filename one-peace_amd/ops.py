@@ -2566,6 +2566,144 @@ def token_mean_norm(x, weight, bias, eps=1e-5):
 
 
 # --------------------------------------------------------------------------------------------------------------
+# video branch (one_peace_vision/video/mmaction_custom/models/backbones/onepeace.py; csrc/frameattn.hip): temporal attention over the
+# frames of a clip on the batch-major rows, the packed q|k|v projection and the spatial attention core as autograd functions
+# --------------------------------------------------------------------------------------------------------------
+def temporal_attention_torch(qkv, B, T, N, heads, scale=None):
+    """onepeace.py:234-247 between the projections and the sub-LayerNorm, as called from :331-337, on the project's rows: qkv
+    [B * T * N, 3 H] packed q | k | v, row (b, t, n).  The two rearranges of :331 and :337 ('n (b t) d -> t (b n) d' and back) as
+    views + copies, q * scaling, bmm, fp32 softmax cast back to the input dtype, bmm.  Returns [B * T * N, H] in the same row order."""
+    R, H3 = qkv.shape
+    H = H3 // 3
+    hd = H // heads
+    if R != B * T * N or H3 != 3 * heads * hd:
+        raise ValueError("temporal_attention: qkv %s is not [B * T * N = %d, 3 * heads * hd]" % (tuple(qkv.shape), B * T * N))
+    scale = hd ** -0.5 if scale is None else scale
+    x = qkv.view(B, T, N, 3, heads, hd).permute(3, 1, 0, 2, 4, 5)                      # [3, T, (B, N, heads), hd]: time-major
+    q, k, v = (t.reshape(T, B * N * heads, hd).transpose(0, 1) for t in x.unbind(0))   # [B * N * heads, T, hd]
+    w = torch.bmm(q * scale, k.transpose(1, 2))
+    p = F.softmax(w, dim=-1, dtype=torch.promote_types(w.dtype, torch.float32)).to(w.dtype)  # (in fp32 for bf16 / fp16 inputs)
+    a = torch.bmm(p, v)                                                                # [(B, N, heads), T, hd]
+    return a.view(B, N, heads, T, hd).permute(0, 3, 1, 2, 4).reshape(R, H)
+
+
+class TemporalAttentionFn(torch.autograd.Function):
+    """op_attn_frames_fwd / op_attn_frames_bwd: the packed q|k|v rows are read where they lie, the output and the packed gradient are
+    written in the same row order; only qkv is kept (the backward recomputes p)."""
+
+    @staticmethod
+    def forward(ctx, qkv, B, T, N, heads, scale):
+        H = qkv.shape[1] // 3
+        out = hip.attn_frames_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, T, N, heads, scale)
+        ctx.save_for_backward(qkv)
+        ctx.dims = (B, T, N, heads, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, = ctx.saved_tensors
+        B, T, N, heads, scale = ctx.dims
+        H = qkv.shape[1] // 3
+        if dout.stride(1) != 1 or dout.stride(0) % 8 or dout.stride(0) < H or dout.data_ptr() % 16:
+            dout = dout.contiguous()
+        return hip.attn_frames_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], dout, B, T, N, heads, scale), None, None, None, None, None
+
+
+def temporal_attention(qkv, B, T, N, heads, scale=None):
+    """[B * T * N, H] = softmax_t'(scale * q_t . k_t') v_t' per (video b, token n, head): self-attention over the T frames of a clip on
+    the packed q|k|v rows [B * T * N, 3 H] (row (b, t, n)).  bf16 CUDA tensors inside the kernels' limits (hip.attn_frames_supported:
+    head_dim 64, T <= 32) run op_attn_frames_fwd / _bwd -- no rearranged copy, p kept in fp32; everything else -- CPU, fp32, fp16,
+    hd != 64, T > 32, unaligned views -- runs temporal_attention_torch."""
+    if qkv.dim() != 2 or qkv.shape[0] != B * T * N or qkv.shape[1] % (3 * heads):
+        raise ValueError("temporal_attention: qkv %s must be [B * T * N = %d, 3 * heads * hd]" % (tuple(qkv.shape), B * T * N))
+    hd = qkv.shape[1] // (3 * heads)
+    scale = hd ** -0.5 if scale is None else float(scale)
+    if hip_eligible(qkv) and hip.attn_frames_supported(qkv, B, T, N, heads, hd):
+        return TemporalAttentionFn.apply(qkv, B, T, N, heads, scale)
+    return temporal_attention_torch(qkv, B, T, N, heads, scale)
+
+
+class PackedQKVFn(torch.autograd.Function):
+    """[R, 3 H] = x [R, H] through q_proj | k_proj | v_proj as ONE GEMM with the three weights as segments (k_proj has no bias).  A
+    frozen weight costs no weight-gradient GEMM and a frozen bias no column sum."""
+
+    @staticmethod
+    def forward(ctx, x, wq, bq, wk, wv, bv):
+        H = wq.shape[0]
+        qkv = hip.gemm_nt(x, [wq, wk, wv], [bq, None, bv], n_seg=H, N=3 * H)
+        ctx.save_for_backward(x if any(ctx.needs_input_grad[i] for i in (1, 3, 4)) else None, wq, wk, wv)
+        ctx.biases = (bq is not None, bv is not None)
+        return qkv
+
+    @staticmethod
+    def backward(ctx, dqkv):
+        x, wq, wk, wv = ctx.saved_tensors
+        H = wq.shape[0]
+        if not dqkv.is_contiguous():
+            dqkv = dqkv.contiguous()
+        need = ctx.needs_input_grad
+        dx = hip.gemm_nt(dqkv, [_transposed((wq, wk, wv))]) if need[0] else None
+        dws = [wgrad(dqkv[:, i * H:(i + 1) * H], x) if need[j] else None for i, j in ((0, 1), (1, 3), (2, 4))]
+        dbq = dbv = None
+        want_q, want_v = ctx.biases[0] and need[2], ctx.biases[1] and need[5]
+        if want_q or want_v:
+            outs = [torch.empty(H, dtype=dqkv.dtype, device=dqkv.device) if w else None for w in (want_q, False, want_v)]
+            hip.colsum_segments(dqkv, H, outs)
+            dbq, dbv = outs[0], outs[2]
+        return dx, dws[0], dbq, dws[1], dws[2], dbv
+
+
+def packed_qkv(x, wq, bq, wk, wv, bv):
+    """x [R, H] bf16 contiguous -> q | k | v [R, 3 H]."""
+    return PackedQKVFn.apply(x, wq, bq, wk, wv, bv)
+
+
+class SpatialAttentionFn(torch.autograd.Function):
+    """The attention core of the fused layer on its own: packed q|k|v [B * S, 3 H] in, [B * S, H] out, over hip.attn_fwd /
+    hip.attn_bwd_launch exactly as _attn_forward / _attn_backward call them (head_dim 64).  bias: a RelPosBias handle or None, a
+    CONSTANT here: the table gets no gradient from this function.  A frozen table is the reference's video fine-tuning state
+    (video/train.py:187-190); when the table requires a gradient the caller takes the torch ops for this product instead
+    (spatial_attention below raises, video_vit.VideoEncoderLayer routes) -- the kernels' own bias-gradient accumulation stays with
+    AttnBranchFn, whose callers it was measured for."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias, B, S, heads, scale):
+        H = heads * 64
+        keep = ctx.needs_input_grad[0]
+        attn, lse = hip.attn_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], qkv.stride(0), B, S, heads, scale,
+                                 bias.image.detach() if bias is not None else None, None, hip.attn_spad(S), want_lse=keep,
+                                 bias_frag=bias.frag if bias is not None and S <= hip.ATTN_RESIDENT_MAX_S else None)
+        if keep:
+            ctx.save_for_backward(qkv, attn, lse)
+        ctx.bias, ctx.dims = bias, (B, S, heads, scale)
+        return attn
+
+    @staticmethod
+    def backward(ctx, dattn):
+        qkv, attn, lse = ctx.saved_tensors
+        B, S, heads, scale = ctx.dims
+        H = heads * 64
+        bias = ctx.bias
+        if not dattn.is_contiguous():
+            dattn = dattn.contiguous()
+        dqkv = torch.empty_like(qkv)
+        _attn_backward(qkv, dattn, attn, lse, B, S, heads, scale, bias.image.detach() if bias is not None else None,
+                       bias.imageT if bias is not None else None, None, None, bias.frag if bias is not None and S <= 384 else None,
+                       dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:])
+        return dqkv, None, None, None, None, None
+
+
+def spatial_attention(qkv, bias, B, S, heads, scale=None):
+    """Attention of B sequences of S tokens on packed q|k|v rows [B * S, 3 * heads * 64] (bf16, device, contiguous) with a shared,
+    FROZEN relative-position bias (RelPosBias handle or None).  -> [B * S, heads * 64]."""
+    if bias is not None and bias.image.requires_grad:
+        raise ValueError("spatial_attention: the relative-position table requires a gradient; this core treats the bias as a constant "
+                         "(take the torch ops, as video_vit.VideoEncoderLayer does)")
+    scale = 64 ** -0.5 if scale is None else float(scale)
+    return SpatialAttentionFn.apply(qkv, bias, B, S, heads, scale)
+
+
+# --------------------------------------------------------------------------------------------------------------
 # pretraining masks (csrc/masks.hip; pretrain_masks.py draws the keys): every random choice is select(candidates, k, keys)
 # --------------------------------------------------------------------------------------------------------------
 def _select_rank(cand, keys, in_row=None):
