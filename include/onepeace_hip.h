@@ -881,6 +881,51 @@ int op_mask_words(const int64_t* src_tokens, int64_t ld, int64_t B, int64_t L, i
 int op_mask_blocks(const int* rows, const int* rows_host, const int* centers, int64_t Kmax, const int* keys, int64_t Tmax, int64_t B,
                    int64_t length, uint8_t* mask, int64_t* ids, int64_t width, void* stream);
 
+/* ---- window attention of the detection branch (csrc/windowattn.hip) -----------------------------------------------------------------
+ * Additive: op_abi_version() stays 10, no existing entry point changed.
+ * op_attn_window_fwd replaces one_peace_vision/det/models/onepeace.py:197-213 (MultiheadAttention.forward between its projections and
+ * the sub-LayerNorm) as called from :308-325 in a window block, INCLUDING window_partition and window_unpartition (:310, :325), the
+ * expanded window bias of :398-401 and add_decomposed_rel_pos (:207): self-attention inside the 16 x 16 windows of a token map, one
+ * sequence of 256 tokens per (sample b, window, head h).  op_attn_window_bwd replaces the autograd backward of those lines.
+ * Layout: every activation tensor is bf16; element (b, y, x, h, d) lies at ((b * Hg + y) * Wg + x) * ld + 64 h + d (strides in
+ * elements): the project's batch-major rows of a [B, Hg, Wg, D] map.  q, k, v share ld (the three column blocks of one packed [R, 3 H]
+ * projection output), out and dout use ldo, dq / dk / dv use ldg and may be the blocks of one packed gradient matrix.  Window (wy, wx)
+ * holds y in [16 wy, 16 wy + 16) and x likewise; the in-window index is i = 16 (y % 16) + x % 16 (detectron2's window_partition order).
+ * bias: bf16 [heads][256][256], query-major, shared by all windows and samples, or NULL.  rel_h, rel_w: bf16 [31][64], shared by all
+ * heads, or NULL together.
+ *   forward   s[i][j] = scale * (q_i . k_j) + bias[h][i][j] + q_i . rel_h[iy - jy + 15] + q_i . rel_w[ix - jx + 15] in fp32, the UNSCALED
+ *             q in the last two terms (:204-207);  p = softmax over the 256 keys, the maximum subtracted;  out = p v, rounded to bf16
+ *             once.
+ *   backward  s and p are RECOMPUTED from q, k, v, bias, rel_*: nothing else is kept from the forward.  dp = dout . v,
+ *             c = sum_j p dp in fp32 from the resident p and dp (never from a rounded out),  ds = p (dp - c),  dv = p^T dout,
+ *             dk = scale * ds^T q,  dTh[i][jy] = sum_jx ds[i][(jy, jx)],  dTw[i][jx] = sum_jy ds[i][(jy, jx)],
+ *             dq_i = scale * sum_j ds k_j + sum_jy dTh[i][jy] rel_h[iy - jy + 15] + sum_jx dTw[i][jx] rel_w[ix - jx + 15].
+ *             EVERY element of [R, heads * 64] of dq, dk and dv is written.
+ *             drel_part (optional): fp32 [parts][2][31][64]; entry (0, r, d) holds sum dTh[i][jy] q_i[d] over the part's share of
+ *             (b, window, head, i, jy) with iy - jy + 15 == r, entry (1, r, d) the same for w.  dbias_slabs (optional): fp32
+ *             [slabs][heads][256][256], each slab the sum of ds over its share of (b, window).  Every element of both is written, by an
+ *             empty share too; the caller sums over the leading axis.  op_attn_window_parts(B, windows, heads, &parts, &slabs) gives
+ *             the two counts (windows = (Hg / 16) * (Wg / 16)).  With a NULL pointer that work is skipped (frozen tables, inference).
+ *             With both NULL the backward runs one workgroup per (b, window, head), as the forward does; dq, dk, dv have the same bits.
+ * STATED DEVIATIONS: every product runs on the matrix pipe (v_mfma_f32_32x32x16_bf16, fp32 accumulation), and these fp32 operands are
+ * rounded to bf16 (to nearest even) first: e = exp(s - max) before e v (the division by sum e follows in fp32);  p before p^T dout;
+ * ds before ds k and ds^T q;  dTh and dTw before the products with rel_h / rel_w (dq) and with q (drel_part).  s, the softmax
+ * statistics, c, ds itself, dTh, dTw and the dbias slabs are fp32.  The backward takes max, sum e and sum e dp tile by tile with a
+ * running maximum (two sweeps over the keys; s is computed twice with the same bits).  exp is v_exp_f32 of (s - max) * log2 e.
+ * No atomics, every sum in a fixed order: two runs give the same bits in every output, and the bits of out, dq, dk, dv of a (b, window,
+ * head) depend on that window's own rows, bias[h], rel_* and scale alone -- not on B, the grid or heads.  Nothing is allocated or
+ * synchronised.
+ * Limits (OP_EINVAL with a message otherwise, checked before the device is touched, nothing launched): hd == 64 and window == 16;
+ * Hg % 16 == 0 and Wg % 16 == 0; ld, ldo, ldg multiples of 8 and >= heads * 64; every pointer that is given aligned to 16 bytes;
+ * B * windows * heads < 2^31.  Offsets are 64-bit.  B == 0 returns without a launch. */
+int op_attn_window_parts(int64_t B, int64_t windows, int64_t heads, int64_t* parts, int64_t* slabs);
+int op_attn_window_fwd(const void* q, const void* k, const void* v, int64_t ld, const void* bias, const void* rel_h, const void* rel_w,
+                       void* out, int64_t ldo, int64_t B, int64_t Hg, int64_t Wg, int64_t heads, int64_t hd, int64_t window, float scale,
+                       void* stream);
+int op_attn_window_bwd(const void* q, const void* k, const void* v, int64_t ld, const void* bias, const void* rel_h, const void* rel_w,
+                       const void* dout, int64_t ldo, void* dq, void* dk, void* dv, int64_t ldg, void* drel_part, void* dbias_slabs,
+                       int64_t B, int64_t Hg, int64_t Wg, int64_t heads, int64_t hd, int64_t window, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

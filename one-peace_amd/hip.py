@@ -123,6 +123,9 @@ SIGNATURES = {
     "op_token_mean_ln_bwd": (c_int, [P, P, P, P, P, P, I64, I64, P, P, I64, I64, I64, P]),
     "op_attn_frames_fwd": (c_int, [P, P, P, I64, P, I64, I64, I64, I64, I64, I64, c_float, P]),
     "op_attn_frames_bwd": (c_int, [P, P, P, I64, P, I64, P, P, P, I64, I64, I64, I64, I64, I64, c_float, P]),
+    "op_attn_window_parts": (c_int, [I64, I64, I64, P, P]),
+    "op_attn_window_fwd": (c_int, [P, P, P, I64, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, c_float, P]),
+    "op_attn_window_bwd": (c_int, [P, P, P, I64, P, P, P, P, I64, P, P, P, I64, P, P, I64, I64, I64, I64, I64, I64, c_float, P]),
     "op_mask_patches": (c_int, [P, P, I64, I64, I64, I64, P, P, P, P, P]),
     "op_mask_words": (c_int, [P, I64, I64, I64, I64, P, I64, P, P, c_float, c_double, P, P, I64, P, P, I64, P, P]),
     "op_mask_blocks": (c_int, [P, P, P, I64, P, I64, I64, I64, P, P, I64, P]),
@@ -1910,6 +1913,92 @@ def attn_frames_bwd(q, k, v, dout, B, T, N, heads, scale, dqkv=None):
     _check(lib().op_attn_frames_bwd(ptr(q), ptr(k), ptr(v), ld, ptr(dout), ldo, ptr(dq), ptr(dk), ptr(dv), ldg, B, T, N, heads, 64, scale,
                                     stream()), "op_attn_frames_bwd")
     return dqkv
+
+
+ATTN_WINDOW = 16  # csrc/windowattn.hip: 16 x 16 windows, 256 keys of 64 dims
+
+
+def attn_window_supported(qkv, B, Hg, Wg, heads, hd, window=ATTN_WINDOW):
+    """The limits of op_attn_window_fwd / _bwd for a packed q|k|v matrix [B * Hg * Wg, 3 * heads * hd]."""
+    H = heads * hd
+    if qkv.dim() != 2 or not qkv.is_cuda or qkv.dtype != torch.bfloat16 or tuple(qkv.shape) != (B * Hg * Wg, 3 * H):
+        return False
+    ld = qkv.stride(0) if qkv.shape[0] > 1 else max(qkv.stride(0), 3 * H)
+    return (hd == 64 and window == ATTN_WINDOW and Hg >= 16 and Wg >= 16 and Hg % 16 == 0 and Wg % 16 == 0 and heads >= 1 and B >= 1
+            and B * (Hg // 16) * (Wg // 16) * heads < 2 ** 31 and qkv.stride(1) == 1 and ld % 8 == 0 and ld >= 3 * H
+            and qkv.data_ptr() % 16 == 0)
+
+
+def attn_window_parts(B, Hg, Wg, heads):
+    """(parts, slabs) of op_attn_window_bwd: the leading sizes of drel_part [parts, 2, 31, 64] and dbias_slabs [slabs, heads, 256, 256]."""
+    parts, slabs = ctypes.c_int64(0), ctypes.c_int64(0)
+    _check(lib().op_attn_window_parts(B, (Hg // 16) * (Wg // 16), heads, ctypes.byref(parts), ctypes.byref(slabs)), "op_attn_window_parts")
+    return parts.value, slabs.value
+
+
+def _window_tables(bias, rel_h, rel_w, heads, what):
+    if bias is not None and (not bias.is_cuda or bias.dtype != torch.bfloat16 or tuple(bias.shape) != (heads, 256, 256)
+                             or not bias.is_contiguous()):
+        raise RuntimeError("%s: bias must be a contiguous bf16 CUDA(HIP) tensor [heads, 256, 256]" % what)
+    if (rel_h is None) != (rel_w is None):
+        raise RuntimeError("%s: rel_h and rel_w must be given together" % what)
+    for t in (rel_h, rel_w):
+        if t is not None and (not t.is_cuda or t.dtype != torch.bfloat16 or tuple(t.shape) != (31, 64) or not t.is_contiguous()):
+            raise RuntimeError("%s: rel_h and rel_w must be contiguous bf16 CUDA(HIP) tensors [31, 64]" % what)
+
+
+def attn_window_fwd(q, k, v, bias, rel_h, rel_w, B, Hg, Wg, heads, scale, out=None):
+    """op_attn_window_fwd: q, k, v bf16 [B * Hg * Wg, heads * 64] views sharing one row stride (the column blocks of a packed projection
+    output), rows ordered (b, y, x); bias bf16 [heads, 256, 256] or None; rel_h, rel_w bf16 [31, 64] or None together.  Returns out bf16
+    [B * Hg * Wg, heads * 64] (own row stride when given)."""
+    H, R = heads * 64, B * Hg * Wg
+    ld = _frames_cols(q, H, "q")
+    if _frames_cols(k, H, "k") != ld or _frames_cols(v, H, "v") != ld or not (q.shape[0] == k.shape[0] == v.shape[0] == R):
+        raise RuntimeError("attn_window_fwd: q, k, v must share the row stride and have B * Hg * Wg = %d rows" % R)
+    _window_tables(bias, rel_h, rel_w, heads, "attn_window_fwd")
+    if out is None:
+        out = torch.empty(R, H, dtype=torch.bfloat16, device=q.device)
+    ldo = _frames_cols(out, H, "out")
+    assert out.shape[0] == R
+    _check(lib().op_attn_window_fwd(ptr(q), ptr(k), ptr(v), ld, ptr(bias), ptr(rel_h), ptr(rel_w), ptr(out), ldo, B, Hg, Wg, heads, 64,
+                                    ATTN_WINDOW, scale, stream()), "op_attn_window_fwd")
+    return out
+
+
+def attn_window_bwd(q, k, v, bias, rel_h, rel_w, dout, B, Hg, Wg, heads, scale, dqkv=None, drel_part=None, dbias_slabs=None,
+                    want_drel=False, want_dbias=False):
+    """op_attn_window_bwd: returns (dqkv, drel_part, dbias_slabs).  dqkv bf16 [R, 3 H], dq | dk | dv packed like a fused projection
+    output (every element written).  drel_part fp32 [parts, 2, 31, 64] and dbias_slabs fp32 [slabs, heads, 256, 256] are computed when
+    given or asked for (want_*), else None; the caller sums them over the leading axis.  s and p are recomputed: the forward's output is
+    not needed."""
+    H, R = heads * 64, B * Hg * Wg
+    ld = _frames_cols(q, H, "q")
+    if _frames_cols(k, H, "k") != ld or _frames_cols(v, H, "v") != ld or not (q.shape[0] == k.shape[0] == v.shape[0] == R):
+        raise RuntimeError("attn_window_bwd: q, k, v must share the row stride and have B * Hg * Wg = %d rows" % R)
+    _window_tables(bias, rel_h, rel_w, heads, "attn_window_bwd")
+    ldo = _frames_cols(dout, H, "dout")
+    assert dout.shape[0] == R
+    if dqkv is None:
+        dqkv = torch.empty(R, 3 * H, dtype=torch.bfloat16, device=q.device)
+    assert dqkv.dim() == 2 and tuple(dqkv.shape) == (R, 3 * H)
+    dq, dk, dv = dqkv[:, :H], dqkv[:, H:2 * H], dqkv[:, 2 * H:]
+    ldg = _frames_cols(dq, H, "dq")
+    if want_drel or want_dbias or drel_part is not None or dbias_slabs is not None:   # (the counts are needed for nothing else)
+        parts, slabs = attn_window_parts(B, Hg, Wg, heads)
+    if drel_part is None and want_drel:
+        drel_part = torch.empty(parts, 2, 31, 64, dtype=torch.float32, device=q.device)
+    if dbias_slabs is None and want_dbias:
+        dbias_slabs = torch.empty(slabs, heads, 256, 256, dtype=torch.float32, device=q.device)
+    if drel_part is not None:
+        _req(drel_part, "drel_part", torch.float32)
+        assert tuple(drel_part.shape) == (parts, 2, 31, 64) and drel_part.is_contiguous()
+    if dbias_slabs is not None:
+        _req(dbias_slabs, "dbias_slabs", torch.float32)
+        assert tuple(dbias_slabs.shape) == (slabs, heads, 256, 256) and dbias_slabs.is_contiguous()
+    _check(lib().op_attn_window_bwd(ptr(q), ptr(k), ptr(v), ld, ptr(bias), ptr(rel_h), ptr(rel_w), ptr(dout), ldo, ptr(dq), ptr(dk), ptr(dv),
+                                    ldg, ptr(drel_part), ptr(dbias_slabs), B, Hg, Wg, heads, 64, ATTN_WINDOW, scale, stream()),
+           "op_attn_window_bwd")
+    return dqkv, drel_part, dbias_slabs
 
 
 MASK_MAX_ITEMS = 4096  # csrc/masks.hip: MK_MAX, the items (positions without CLS) of one row

@@ -2895,3 +2895,112 @@ def block_masks(frames, centers, keys, mask_prob, mask_length, mask_prob_adjust=
     f = torch.where(change, ~drop, f)
     m = torch.cat([torch.zeros(B, 1, dtype=torch.bool), f], 1)
     return m, _preserve_ids(m, T.view(B) + 1, width)[0]
+
+
+# --------------------------------------------------------------------------------------------------------------
+# detection branch (one_peace_vision/det/models/onepeace.py; csrc/windowattn.hip): attention inside the 16 x 16 windows of a token map
+# on the batch-major rows, with the shared window bias and the decomposed relative positions
+# --------------------------------------------------------------------------------------------------------------
+def decomposed_rel_index(size, device=None):
+    """detectron2's get_rel_pos for q_size == k_size == size and a table of 2 * size - 1 rows: [size, size] with entry (i, j) = i - j +
+    size - 1, the row of rel_pos that query coordinate i and key coordinate j share."""
+    c = torch.arange(size, device=device)
+    return c[:, None] - c[None, :] + (size - 1)
+
+
+def window_attention_torch(qkv, bias, rel_h, rel_w, B, Hg, Wg, heads, window, scale=None, pad_row=None):
+    """det/models/onepeace.py:197-213 between the projections and the sub-LayerNorm as called from :308-325 in a window block, on the
+    project's rows: qkv [B * Hg * Wg, 3 H] packed q | k | v, row (b, y, x).  window_partition with padding to a multiple of `window`,
+    (q * scale) @ k^T, + bias ([heads, window^2, window^2] or None), add_decomposed_rel_pos with the unscaled q (rel_h, rel_w
+    [2 * window - 1, hd] or None together), fp32 softmax cast back, @ v, window_unpartition and the crop.  detectron2 pads the normed
+    activation with zeros BEFORE the projections, so a padded token's q | k | v is the projection of a zero row -- q_proj.bias | 0 |
+    v_proj.bias in the reference; the caller passes that row as pad_row [3 H].  It defaults to zeros (exact for projections without a
+    bias) and matters only on a grid that is not a multiple of `window`.  Any window size, any grid, CPU, fp32, fp16.  Returns
+    [B * Hg * Wg, H] in the same row order."""
+    R, H3 = qkv.shape
+    H = H3 // 3
+    hd = H // heads
+    if R != B * Hg * Wg or H3 != 3 * heads * hd:
+        raise ValueError("window_attention: qkv %s is not [B * Hg * Wg = %d, 3 * heads * hd]" % (tuple(qkv.shape), B * Hg * Wg))
+    scale = hd ** -0.5 if scale is None else scale
+    w = int(window)
+    ph, pw = (w - Hg % w) % w, (w - Wg % w) % w
+    Hp, Wp = Hg + ph, Wg + pw
+    x = qkv.view(B, Hg, Wg, H3)
+    if ph or pw:
+        full = (qkv.new_zeros(H3) if pad_row is None else pad_row.to(qkv.dtype)).expand(B, Hp, Wp, H3).clone()
+        full[:, :Hg, :Wg] = x
+        x = full
+    nh, nw = Hp // w, Wp // w
+    x = x.view(B, nh, w, nw, w, 3, heads, hd).permute(5, 0, 1, 3, 6, 2, 4, 7).reshape(3, B * nh * nw * heads, w * w, hd)
+    q, k, v = x.unbind(0)
+    attn = torch.bmm(q * scale, k.transpose(1, 2))
+    if bias is not None:
+        attn = (attn.view(-1, heads, w * w, w * w) + bias.to(attn.dtype)).view(-1, w * w, w * w)
+    if rel_h is not None:
+        idx = decomposed_rel_index(w, qkv.device)
+        rq = q.reshape(-1, w, w, hd)
+        th = torch.einsum("bhwc,hkc->bhwk", rq, rel_h.to(q.dtype)[idx])
+        tw = torch.einsum("bhwc,wkc->bhwk", rq, rel_w.to(q.dtype)[idx])
+        attn = (attn.view(-1, w, w, w, w) + th[:, :, :, :, None] + tw[:, :, :, None, :]).view(-1, w * w, w * w)
+    p = F.softmax(attn, dim=-1, dtype=torch.promote_types(attn.dtype, torch.float32)).to(attn.dtype)
+    a = torch.bmm(p, v)                                                                # [(B, nh, nw, heads), w * w, hd]
+    a = a.view(B, nh, nw, heads, w, w, hd).permute(0, 1, 4, 2, 5, 3, 6).reshape(B, Hp, Wp, H)
+    return a[:, :Hg, :Wg].reshape(R, H)
+
+
+class WindowAttentionFn(torch.autograd.Function):
+    """op_attn_window_fwd / op_attn_window_bwd: the packed q|k|v rows are read where they lie, the output and the packed gradient are
+    written in the same row order; only the inputs are kept (the backward recomputes s and p).  Gradients for qkv, bias (the sum of the
+    kernel's slabs, cast to bias.dtype), rel_h and rel_w (the sum of its parts); slabs and parts are asked for only where
+    needs_input_grad says so."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias, rel_h, rel_w, B, Hg, Wg, heads, scale):
+        H = qkv.shape[1] // 3
+        bias_k = None if bias is None else bias.detach().to(torch.bfloat16).contiguous()
+        rel_hk = None if rel_h is None else rel_h.detach().to(torch.bfloat16).contiguous()
+        rel_wk = None if rel_w is None else rel_w.detach().to(torch.bfloat16).contiguous()
+        out = hip.attn_window_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], bias_k, rel_hk, rel_wk, B, Hg, Wg, heads, scale)
+        ctx.save_for_backward(qkv, bias_k, rel_hk, rel_wk)
+        ctx.dims = (B, Hg, Wg, heads, scale)
+        ctx.dtypes = (None if bias is None else bias.dtype, None if rel_h is None else rel_h.dtype, None if rel_w is None else rel_w.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, bias, rel_h, rel_w = ctx.saved_tensors
+        B, Hg, Wg, heads, scale = ctx.dims
+        H = qkv.shape[1] // 3
+        if dout.stride(1) != 1 or dout.stride(0) % 8 or dout.stride(0) < H or dout.data_ptr() % 16:
+            dout = dout.contiguous()
+        need = ctx.needs_input_grad
+        want_dbias = bias is not None and need[1]
+        want_drel = rel_h is not None and (need[2] or need[3])
+        dqkv, parts, slabs = hip.attn_window_bwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], bias, rel_h, rel_w, dout, B, Hg, Wg, heads,
+                                                 scale, want_drel=want_drel, want_dbias=want_dbias)
+        dbias = slabs.sum(0).to(ctx.dtypes[0]) if want_dbias else None
+        drel = parts.sum(0) if want_drel else None
+        drel_h = drel[0].to(ctx.dtypes[1]) if want_drel and need[2] else None
+        drel_w = drel[1].to(ctx.dtypes[2]) if want_drel and need[3] else None
+        return dqkv if need[0] else None, dbias, drel_h, drel_w, None, None, None, None, None
+
+
+def window_attention(qkv, bias, rel_h, rel_w, B, Hg, Wg, heads, window, scale=None, pad_row=None):
+    """[B * Hg * Wg, H]: softmax attention inside the window x window windows of a [B, Hg, Wg] token map on the packed q|k|v rows
+    [B * Hg * Wg, 3 H] (row (b, y, x)), with the shared bias [heads, window^2, window^2] and the decomposed relative positions rel_h,
+    rel_w [2 * window - 1, hd] (each may be None; rel_h and rel_w together).  bf16 CUDA tensors inside the kernels' limits
+    (hip.attn_window_supported: head_dim 64, window 16, a grid of multiples of 16) run op_attn_window_fwd / _bwd -- no partitioned copy,
+    no expanded bias, s and p in fp32; everything else -- CPU, fp32, fp16, other windows, grids that need padding -- runs
+    window_attention_torch (see there for pad_row)."""
+    if qkv.dim() != 2 or qkv.shape[0] != B * Hg * Wg or qkv.shape[1] % (3 * heads):
+        raise ValueError("window_attention: qkv %s must be [B * Hg * Wg = %d, 3 * heads * hd]" % (tuple(qkv.shape), B * Hg * Wg))
+    if (rel_h is None) != (rel_w is None):
+        raise ValueError("window_attention: rel_h and rel_w must be given together")
+    hd = qkv.shape[1] // (3 * heads)
+    scale = hd ** -0.5 if scale is None else float(scale)
+    tables = [t for t in (bias, rel_h, rel_w) if t is not None]
+    if (hip_eligible(qkv) and all(t.is_cuda for t in tables) and hip.attn_window_supported(qkv, B, Hg, Wg, heads, hd, window)
+            and (bias is None or tuple(bias.shape) == (heads, 256, 256))):
+        return WindowAttentionFn.apply(qkv, bias, rel_h, rel_w, B, Hg, Wg, heads, scale)
+    return window_attention_torch(qkv, bias, rel_h, rel_w, B, Hg, Wg, heads, window, scale, pad_row)
